@@ -15,6 +15,11 @@ At world>1 the embeddings default to table-sharded EP (static all-to-all
 routing); --emb-mode dp selects replicated arenas + sparse allgather.
 Synthetic data (no network), random-init weights, weak scaling (per-GPU
 batch fixed).
+
+A plain run does only the above.  --dump-outputs DIR additionally writes,
+after the timed loop, what the last timed step computed (see dump_outputs).
+--full is the switch for every measurement beyond the headline figure; the
+headline is all this script measures today, so it currently adds nothing.
 """
 import argparse
 import json
@@ -22,6 +27,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -58,6 +64,93 @@ def make_batches(device, batch, rank, dtype, vocab=VOCAB, n_cat=N_CAT):
     return batches
 
 
+DUMP_SAMPLES = 256      # samples of the last batch whose arena rows are dumped
+DUMP_DENSE = 65536      # dense parameters dumped
+
+
+def dump_outputs(out_dir, loss, logits, flat, model, cats):
+    """Write what the last timed step computed as float32 <out_dir>/*.npy
+    (~2.5 MB at the headline config):
+
+      loss            [1]      what step() returns: the batch loss
+      logits          [B]      the model's forward output for the last batch
+      dense_index     [K]      positions of a fixed seeded sample of the flat
+                               dense parameters (float64 ids)
+      dense_params    [K]      their values after the update
+      emb<k>_rows     [S*F]    arena rows looked up by a fixed seeded sample
+                               of S samples of the last batch (float64 ids)
+      emb<k>_weights  [S*F,.]  those rows after the update (unified arena:
+                               the D deep columns + the wide column)
+      emb<k>_adagrad  [S*F]    unified arena only: the rows' decoded in-row
+                               rowwise-adagrad accumulators
+
+    EP-sharded arenas (world>1) dump a seeded sample of local rows instead.
+
+    Inputs and initial weights are seeded, and the CPU path repeats bit for
+    bit.  On the GPU the update kernels accumulate with atomics (embedding
+    scatter, bias grads): ONE step repeats to rounding, but bf16
+    re-quantisation and Adam's normalisation grow that noise step by step,
+    fastest while the resident batches are being memorised, so compare two
+    builds against the spread between two runs of one build.  Measured
+    spread between identical runs on one MI355X, max |a-b| (value range):
+
+                       --steps 20 --warmup 5      --steps 50 --warmup 10
+      loss             4.4e-5  (0.0192)           1.8e-6  (1.3e-5)
+      logits           0.19    (-14..17)          2.1     (-31..34)
+      dense_params     4.5e-3  (-0.15..0.10)      5.9e-3  (-0.15..0.11)
+      emb0_weights     7.8e-3  (-1.25..1.25)      7.8e-3  (-1.3..1.24)
+      emb0_adagrad     7.3e-12 (0..2.8e-10)       1.9e-11 (0..3.6e-10)
+
+    (three runs each, largest pairwise difference; the mean differences are
+    10-100x smaller: logits 0.017 / 0.12, dense_params 2.6e-4 / 3.3e-4.)
+    The spread keeps growing with the step count, and the loss falls towards
+    zero as the 8 resident batches are memorised (1e-5 after 60 steps, 1e-6
+    after ~200), so its RELATIVE spread grows too (0.2% at 25 steps, 14% at
+    60): compare the loss absolutely, and prefer few steps for comparing."""
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, t, dtype=np.float32):
+        a = t.detach().to("cpu", torch.float64).numpy().astype(dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+    save("loss", loss.reshape(1))
+    save("logits", logits.reshape(-1))
+    gen = torch.Generator(device="cpu").manual_seed(4321)
+    n = flat.flat.numel()
+    didx = torch.randperm(n, generator=gen)[:DUMP_DENSE].sort().values
+    save("dense_index", didx, np.float64)
+    save("dense_params", flat.flat[didx.to(flat.flat.device)])
+    pick = torch.randperm(cats.shape[0], generator=gen)[:DUMP_SAMPLES]
+    k = 0
+    for _, m in sorted(model.named_modules(), key=lambda kv: kv[0]):
+        arena = getattr(m, "arena", None)
+        if not getattr(arena, "_is_embedding_arena", False):
+            continue
+        offsets = getattr(m, "offsets", None)
+        sizes = getattr(m, "sizes", None)
+        if (offsets is not None and sizes is not None
+                and offsets.numel() == cats.shape[1]
+                and int(sizes.sum()) == arena.shape[0]):
+            ids = cats[pick.to(cats.device)]
+            rows = (ids.clamp(min=0) % sizes + offsets).reshape(-1)
+        else:
+            nr = min(arena.shape[0], DUMP_SAMPLES * cats.shape[1])
+            rows = torch.randperm(arena.shape[0], generator=gen)[:nr].to(arena.device)
+        vals = arena.data[rows]
+        save(f"emb{k}_rows", rows, np.float64)
+        if getattr(arena, "_acc_in_arena", False):
+            D = arena._unified_split
+            save(f"emb{k}_weights", vals[:, :D + 1])
+            if vals.dtype == torch.bfloat16:
+                acc = vals[:, D + 2:D + 4].contiguous().view(torch.float32)
+            else:
+                acc = vals[:, D + 2]
+            save(f"emb{k}_adagrad", acc.reshape(-1))
+        else:
+            save(f"emb{k}_weights", vals)
+        k += 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -80,7 +173,16 @@ def main():
                          "(dp), feature-sharded static all-to-all (ep, the "
                          "default at world>1), or row%%world sharding "
                          "(ep_row)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "step computed as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline "
+                         "figure (none today: the plain run is the whole "
+                         "benchmark)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     rank, world, device = init_distributed()
     if args.gpus != 1 and args.gpus != world:
@@ -128,6 +230,7 @@ def main():
 
     use_graphs = (args.graphs == "on" or
                   (args.graphs == "auto" and on_gpu and world == 1))
+    last = {}  # logits of the most recent step (a static buffer under graphs)
 
     if use_graphs:
         # static input buffers; per step we copy the rotating batch in and
@@ -137,6 +240,7 @@ def main():
 
         def graph_body():
             logits = model(sdense, scats)
+            last["logits"] = logits.detach()
             loss = weighted_loss(logits, starget, sweight, "sigmoid_ce")
             loss.backward()
             agg.finish()
@@ -163,6 +267,7 @@ def main():
         def step(i):
             dense, cats, target, weight = batches[i % N_BATCHES]
             logits = model(dense, cats)
+            last["logits"] = logits.detach()
             loss = weighted_loss(logits, target, weight, "sigmoid_ce")
             loss.backward()
             agg.finish()
@@ -179,7 +284,7 @@ def main():
         torch.cuda.synchronize()
     t0 = time.time()
     for i in range(args.steps):
-        step(args.warmup + i)
+        loss = step(args.warmup + i)
     if on_gpu:
         torch.cuda.synchronize()
     if is_distributed():
@@ -224,6 +329,10 @@ def main():
                 "arena": args.arena,
             },
         }
+        if args.dump_outputs:
+            last_cats = batches[(args.warmup + args.steps - 1) % N_BATCHES][1]
+            dump_outputs(args.dump_outputs, loss, last["logits"], flat, model,
+                         last_cats)
         print(json.dumps(out), flush=True)
     destroy_distributed()
 

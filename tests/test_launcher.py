@@ -140,7 +140,7 @@ def test_launcher_ep_restart_resumes_from_shards(tmp_path):
                    tmp_model_path=str(tmp_path / "ckpt"),
                    final_model_path=str(tmp_path / "final"),
                    model_type="wide_deep", embed_dim=4, device="cpu",
-                   batch_size=32, max_rank_restarts=2,
+                   backend="gloo", batch_size=32, max_rank_restarts=2,
                    master_port=29763)
     la = Launcher(rc, mc, _ep_crash_once_entry)
     stats = la.run()

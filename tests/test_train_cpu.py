@@ -81,8 +81,10 @@ def test_resume_from_checkpoint(tmp_path):
 def test_export_scorer_roundtrip(tmp_path):
     train, valid = _data(n=600)
     mc = _mc(epochs=1)
+    # device="cpu": the parity checks below feed CPU tensors to the trained
+    # model, also where a GPU is visible
     rc = RunConfig(tmp_model_path=str(tmp_path / "ckpt"),
-                   final_model_path=str(tmp_path / "final"))
+                   final_model_path=str(tmp_path / "final"), device="cpu")
     model = ShifuMLP(10, [16, 8], ["relu", "relu"], seed=3)
     tr = Trainer(model, mc, rc, train, valid)
     tr.fit()
@@ -108,7 +110,7 @@ def test_embedding_models_learn(tmp_path, cls):
     train, valid = _data(n=1500, n_dense=6, vocab=(30, 50), seed=11)
     mc = _mc(epochs=4, lr=0.02)
     rc = RunConfig(tmp_model_path=str(tmp_path / "ckpt"),
-                   final_model_path=str(tmp_path / "final"))
+                   final_model_path=str(tmp_path / "final"), device="cpu")
     model = cls(6, [30, 50], 8, [16, 8], ["relu", "relu"], seed=2)
     tr = Trainer(model, mc, rc, train, valid)
     first = tr.evaluate(tr.valid_data)
@@ -254,7 +256,8 @@ def test_resume_equivalence_cpu(tmp_path):
 
     def run(epochs, sub):
         rc = RunConfig(tmp_model_path=str(tmp_path / sub / "ckpt"),
-                       final_model_path=str(tmp_path / sub / "final"))
+                       final_model_path=str(tmp_path / sub / "final"),
+                       device="cpu")
         model = ShifuMLP(10, [16, 8], ["relu", "relu"], seed=3)
         tr = Trainer(model, _mc(epochs=epochs), rc, train, valid)
         tr.fit()
@@ -263,7 +266,8 @@ def test_resume_equivalence_cpu(tmp_path):
     straight = run(4, "a").evaluate(run(4, "a2").valid_data)["loss"]
 
     rc_b = RunConfig(tmp_model_path=str(tmp_path / "b" / "ckpt"),
-                     final_model_path=str(tmp_path / "b" / "final"))
+                     final_model_path=str(tmp_path / "b" / "final"),
+                     device="cpu")
     m1 = ShifuMLP(10, [16, 8], ["relu", "relu"], seed=3)
     Trainer(m1, _mc(epochs=2), rc_b, train, valid).fit()
     m2 = ShifuMLP(10, [16, 8], ["relu", "relu"], seed=3)
