@@ -19,7 +19,8 @@ setup(
     ext_modules=[
         CUDAExtension(
             name="shifu_amd.ops._shifu_hip",
-            sources=["shifu_amd/ops/hip/shifu_ops.hip"],
+            sources=["shifu_amd/ops/hip/shifu_ops.hip",
+                     "shifu_amd/ops/hip/fused_mlp.hip"],
             extra_compile_args={
                 "cxx": ["-O3", "-std=c++17"],
                 "nvcc": ["-O3", "-std=c++17", "--offload-arch=gfx950"],

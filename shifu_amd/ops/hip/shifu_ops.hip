@@ -3503,6 +3503,11 @@ at::Tensor fm2_bwd(at::Tensor emb, at::Tensor s, at::Tensor dout, long F, long D
   return demb;
 }
 
+// whole-network MLP scoring kernel — defined in fused_mlp.hip
+at::Tensor mlp_score_fused(at::Tensor x, at::Tensor packed,
+                           at::Tensor layer_table, int64_t max_blocks,
+                           int64_t waves);
+
 // ---------------------------------------------------------------------------
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "shifu_amd CDNA4 (gfx950) kernels";
@@ -3544,4 +3549,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("emb_update_unified_binned", &emb_update_unified_binned);
   m.def("emb_sgd_step", &emb_sgd_step);
   m.def("emb_adagrad_step", &emb_adagrad_step);
+  m.def("mlp_score_fused", &mlp_score_fused, py::arg("x"), py::arg("packed_weights"),
+        py::arg("layer_table"), py::arg("max_blocks") = 0, py::arg("waves") = 8);
 }

@@ -8,6 +8,7 @@ score per row, and optionally report AUC against the target column.
     python -m shifu_amd.score --model final_model/ \
         --data part-*.csv.gz --column-config ColumnConfig.json \
         --output scores.csv [--auc] [--batch 65536] [--device cpu|cuda]
+        [--fused off|on|auto]
 
 Without --column-config the row layout is assumed to be the exported feature
 order (num_dense floats, then categorical ids) with no target/weight columns.
@@ -34,13 +35,14 @@ import numpy as np
 
 def score_files(model_dir: str, data_paths: List[str],
                 column_config: Optional[str] = None, batch: int = 65536,
-                device: str = "cpu", delimiter: str = "|"):
-    """Returns (scores np[N], targets np[N] or None)."""
+                device: str = "cpu", delimiter: str = "|", fused=False):
+    """Returns (scores np[N], targets np[N] or None).  fused: False | True |
+    "auto" — the single-kernel MLP scoring path (see load_exported)."""
     import torch
     from shifu_amd.train.export import load_exported
     from shifu_amd.io import load_csv_native
 
-    model = load_exported(model_dir, device=device)
+    model = load_exported(model_dir, device=device, fused=fused)
     with open(f"{model_dir}/graph.json") as f:
         spec = json.load(f)
     nd = int(spec["num_dense"])
@@ -92,6 +94,9 @@ def main(argv=None) -> int:
     ap.add_argument("--batch", type=int, default=65536)
     ap.add_argument("--device", default="cpu")
     ap.add_argument("--delimiter", default="|")
+    ap.add_argument("--fused", choices=["off", "on", "auto"], default="off",
+                    help="single-kernel scoring for MLP bundles: 'on' errors "
+                         "on an ineligible bundle, 'auto' keeps the layer path")
     ap.add_argument("--auc", action="store_true",
                     help="also print AUC vs the target column (needs --column-config)")
     args = ap.parse_args(argv)
@@ -116,7 +121,9 @@ def main(argv=None) -> int:
         import torch
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", rank)))
     scores, targets = (score_files(args.model, my_paths, args.column_config,
-                                   args.batch, args.device, args.delimiter)
+                                   args.batch, args.device, args.delimiter,
+                                   fused={"off": False, "on": True,
+                                          "auto": "auto"}[args.fused])
                        if my_paths else (np.empty(0), None))
 
     if args.output == "-" and world == 1:

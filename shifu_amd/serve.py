@@ -37,7 +37,10 @@ class ShifuScorer:
         self.num_cat = 0
         self.device = "cpu"
 
-    def init(self, generic_model_config_path: str, device: str = "cpu") -> None:
+    def init(self, generic_model_config_path: str, device: str = "cpu",
+             fused=False) -> None:
+        """fused (False | True | "auto") is forwarded to load_exported: the
+        single-kernel MLP scoring path (ops/fused_mlp.py)."""
         with open(generic_model_config_path) as f:
             gmc = json.load(f)
         if gmc.get("outputnames", ["shifu_output_0"])[0] != "shifu_output_0":
@@ -49,7 +52,7 @@ class ShifuScorer:
         gj = os.path.join(model_path, "graph.json")
         if os.path.exists(gj):
             from shifu_amd.train.export import load_exported
-            self.model = load_exported(model_path, device=device)
+            self.model = load_exported(model_path, device=device, fused=fused)
             self.device = device
             with open(gj) as f:
                 spec = json.load(f)
@@ -59,6 +62,9 @@ class ShifuScorer:
         # no portable layout: score straight from the TF SavedModel artifact
         # (the same file the Java SavedModelBundle path loads)
         pb = os.path.join(model_path, "saved_model.pb")
+        if fused is True:
+            raise ValueError(f"{model_path}: fused scoring needs the portable "
+                             f"graph.json bundle")
         if not os.path.exists(pb):
             raise FileNotFoundError(
                 f"{model_path}: neither graph.json nor saved_model.pb")

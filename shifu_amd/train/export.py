@@ -119,8 +119,16 @@ def export_model(model: torch.nn.Module, final_model_path: str,
     return final_model_path
 
 
-def load_exported(final_model_path: str, device: str = "cpu") -> torch.nn.Module:
-    """Reconstruct an exported model from graph.json + weights (the scorer path)."""
+def load_exported(final_model_path: str, device: str = "cpu",
+                  fused=False) -> torch.nn.Module:
+    """Reconstruct an exported model from graph.json + weights (the scorer path).
+
+    fused=True routes predict() of an eligible `mlp` bundle through the
+    single-kernel scoring path (ops/fused_mlp.py) and raises ValueError with
+    the reason on an ineligible one; fused="auto" quietly keeps the layer
+    path there; fused=False (default) never touches the fused path."""
+    if fused not in (False, True, "auto"):
+        raise ValueError(f"fused must be False, True or 'auto', got {fused!r}")
     from shifu_amd.models.mlp import ShifuMLP
     from shifu_amd.models.wide_deep import WideDeep
     from shifu_amd.models.deepfm import DeepFM
@@ -146,4 +154,13 @@ def load_exported(final_model_path: str, device: str = "cpu") -> torch.nn.Module
         state = torch.load(os.path.join(final_model_path, "model.pt"),
                            map_location="cpu", weights_only=True)
     model.load_state_dict(state)
-    return model.to(device).eval()
+    model = model.to(device).eval()
+    if fused:
+        from shifu_amd.ops.fused_mlp import attach_fused, fused_eligible
+        ok, why = fused_eligible(model)
+        if ok:
+            attach_fused(model)
+        elif fused is True:
+            raise ValueError(f"{final_model_path}: fused scoring unavailable "
+                             f"for this {fam} bundle: {why}")
+    return model
