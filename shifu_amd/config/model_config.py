@@ -75,6 +75,7 @@ class ModelConfig:
     algorithm: str = "NN"
     model_name: str = "model"
     data_delimiter: str = "|"
+    bagging_num: int = 1       # train.baggingNum: members of the bagged model set
     raw: Dict[str, Any] = field(default_factory=dict)
 
     @classmethod
@@ -104,6 +105,7 @@ class ModelConfig:
             algorithm=str(train.get("algorithm", "NN")),
             model_name=str(basic.get("name", "model")),
             data_delimiter=str(ds.get("dataDelimiter", "|")),
+            bagging_num=int(train.get("baggingNum", 1)),
             raw=d,
         )
 
@@ -119,6 +121,7 @@ class ModelConfig:
             "train": {
                 "numTrainEpochs": self.num_train_epochs,
                 "validSetRate": self.valid_set_rate,
+                "baggingNum": self.bagging_num,
                 "algorithm": self.algorithm,
                 "params": {
                     "NumHiddenLayers": self.params.num_hidden_layers,

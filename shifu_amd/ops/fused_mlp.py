@@ -172,3 +172,189 @@ def attach_fused(model) -> PackedMLP:
     model._fused_packed = packed
     model.predict = lambda dense, cats=None: fused_predict(packed, dense)
     return packed
+
+
+# ---------------------------------------------------------------------------
+# Bagged ensembles (Shifu train.baggingNum -> model0 .. modelN-1, mean score).
+#
+# `mlp_score_fused_ensemble` keeps the packed images of a whole GROUP of
+# member networks in LDS, loads each 16-row tile's layer-0 fragments once and
+# runs every member on them: M members cost one read of the rows and one
+# launch.  Members that do not fit one block's LDS together are split
+# greedily, in member order, into consecutive groups (one launch each); the
+# running fp32 sum is carried from launch to launch in the output buffer and
+# scaled once at the end, so the result does not depend on the grouping.
+
+MAX_ENSEMBLE = 64             # members over all groups
+MAX_GROUP_MEMBERS = 8         # members resident in LDS per launch
+MAX_GROUP_LAYERS = 32         # layers (heads included) per launch
+MAX_ENSEMBLE_INPUT = 512      # layer-0 fragments stay live across all members
+
+
+def _shapes_of(model) -> List[Tuple[int, int]]:
+    return [(l.out_features, l.in_features) for l in _layers_of(model)]
+
+
+def _blob_bytes(shapes: List[Tuple[int, int]]) -> int:
+    return sum(_ceil_to(n, 16) * _ceil_to(k, 32) * 2 + _ceil_to(n, 16) * 4
+               for n, k in shapes)
+
+
+def _group_lds_bytes(group_shapes: List[List[Tuple[int, int]]],
+                     max_kpad: int) -> int:
+    """`_lds_bytes` arithmetic for a group: the members' blobs back to back
+    plus the 8 waves' ping-pong buffers at the ensemble-wide hidden Kpad."""
+    return sum(_blob_bytes(s) for s in group_shapes) + 2 * WAVES * 32 * max_kpad
+
+
+def _ensemble_max_kpad(all_shapes: List[List[Tuple[int, int]]]) -> int:
+    return max([32] + [_ceil_to(k, 32) for s in all_shapes for _, k in s[1:]])
+
+
+def ensemble_eligible(models) -> Tuple[bool, str]:
+    """(True, "") when `models` can run as one fused ensemble, else
+    (False, reason)."""
+    models = list(models)
+    if not 1 <= len(models) <= MAX_ENSEMBLE:
+        return False, (f"{len(models)} members, the fused ensemble kernel "
+                       f"takes 1..{MAX_ENSEMBLE}")
+    for i, m in enumerate(models):
+        ok, why = fused_eligible(m)
+        if not ok:
+            return False, f"member {i}: {why}"
+    widths = [_layers_of(m)[0].in_features for m in models]
+    if len(set(widths)) != 1:
+        return False, (f"members disagree on the input width: {widths} (one "
+                       f"set of layer-0 fragments feeds every member)")
+    if widths[0] > MAX_ENSEMBLE_INPUT:
+        return False, (f"input width {widths[0]} > {MAX_ENSEMBLE_INPUT} (the "
+                       f"layer-0 fragments stay in registers across all members)")
+    shapes = [_shapes_of(m) for m in models]
+    max_kpad = _ensemble_max_kpad(shapes)
+    for i, s in enumerate(shapes):
+        lds = _group_lds_bytes([s], max_kpad)
+        if lds > LDS_LIMIT:
+            return False, (f"member {i}: packed weights + the ensemble's "
+                           f"activation buffers need {lds} B of LDS > {LDS_LIMIT}")
+    return True, ""
+
+
+@dataclass
+class PackedEnsemble:
+    blobs: List[torch.Tensor]   # per group: uint8, the members' images back to back
+    tables: List[torch.Tensor]  # per group: CPU int32 [Lg, 5]: member index in
+                                # the group, byte offset, N, K, act id
+    group_sizes: List[int]      # members per group, in member order
+    group_lds_bytes: List[int]  # LDS of each group's 8-wave block
+    num_features: int
+    num_members: int
+
+
+def pack_ensemble(models, max_group_bytes: int = LDS_LIMIT) -> PackedEnsemble:
+    """Pack `models` (member order = summation order) into LDS-sized groups.
+    max_group_bytes lowers the per-group LDS budget (tests force more groups)."""
+    models = list(models)
+    ok, why = ensemble_eligible(models)
+    if not ok:
+        raise ValueError(f"models are not eligible for fused ensemble scoring: {why}")
+    budget = min(int(max_group_bytes), LDS_LIMIT)
+    shapes = [_shapes_of(m) for m in models]
+    max_kpad = _ensemble_max_kpad(shapes)
+
+    groups: List[List[int]] = [[]]
+    for i, s in enumerate(shapes):
+        if _group_lds_bytes([s], max_kpad) > budget:
+            raise ValueError(f"member {i} alone needs "
+                             f"{_group_lds_bytes([s], max_kpad)} B of LDS > "
+                             f"max_group_bytes={budget}")
+        cur = groups[-1]
+        trial = [shapes[j] for j in cur] + [s]
+        if cur and (len(trial) > MAX_GROUP_MEMBERS
+                    or sum(len(t) for t in trial) > MAX_GROUP_LAYERS
+                    or _group_lds_bytes(trial, max_kpad) > budget):
+            groups.append([i])
+        else:
+            cur.append(i)
+
+    device = _layers_of(models[0])[0].weight.device
+    blobs, tables, lds = [], [], []
+    for g in groups:
+        parts, rows, off = [], [], 0
+        for mi, i in enumerate(g):
+            pm = pack_mlp(models[i])
+            parts.append(pm.blob.cpu())
+            for o, n, k, act in pm.table.tolist():
+                rows.append([mi, off + o, n, k, act])
+            off += pm.blob.numel()
+        blobs.append(torch.cat(parts).contiguous().to(device))
+        tables.append(torch.tensor(rows, dtype=torch.int32))
+        lds.append(_group_lds_bytes([shapes[i] for i in g], max_kpad))
+    return PackedEnsemble(blobs=blobs, tables=tables,
+                          group_sizes=[len(g) for g in groups],
+                          group_lds_bytes=lds,
+                          num_features=_layers_of(models[0])[0].in_features,
+                          num_members=len(models))
+
+
+def ensemble_members(packed: PackedEnsemble) -> List[PackedMLP]:
+    """Each member as a stand-alone PackedMLP cut out of its group's blob
+    (CPU), in member order — the per-model layout `pack_mlp` builds."""
+    out = []
+    for blob, table in zip(packed.blobs, packed.tables):
+        blob = blob.cpu()
+        rows = table.tolist()
+        for mi in range(rows[-1][0] + 1):
+            mine = [r[1:] for r in rows if r[0] == mi]
+            base = mine[0][0]
+            end = base + _blob_bytes([(n, k) for _, n, k, _ in mine])
+            out.append(PackedMLP(
+                blob=blob[base:end].clone(),
+                table=torch.tensor([[o - base, n, k, a] for o, n, k, a in mine],
+                                   dtype=torch.int32),
+                lds_bytes=_lds_bytes([(n, k) for _, n, k, _ in mine]),
+                num_features=packed.num_features))
+    return out
+
+
+def _emulate_ensemble(packed: PackedEnsemble, dense: torch.Tensor):
+    """(mean [B], members [B, M]) with the kernel's arithmetic: per-member
+    `_emulate`, fp32 left-to-right sum in member order, times float32(1/M)."""
+    cols = [_emulate(pm, dense).float() for pm in ensemble_members(packed)]
+    total = torch.zeros_like(cols[0])
+    for c in cols:
+        total = total + c
+    scale = torch.tensor(1.0 / packed.num_members, dtype=torch.float32)
+    return total * scale.to(total.device), torch.stack(cols, dim=1)
+
+
+@torch.no_grad()
+def fused_ensemble_predict(packed: PackedEnsemble, dense: torch.Tensor,
+                           return_members: bool = False, max_blocks: int = 0,
+                           waves: int = WAVES):
+    """Mean score fp32 [B] over the members for dense [B, num_features]; with
+    return_members=True, (mean [B], per-member scores [B, M])."""
+    if dense.dim() != 2 or dense.shape[1] != packed.num_features:
+        raise ValueError(f"expected dense [B, {packed.num_features}], got "
+                         f"{tuple(dense.shape)}")
+    ext = require_hip() if dense.is_cuda else None
+    if ext is None:            # CPU rows, or the explicit eager A/B opt-in
+        mean, members = _emulate_ensemble(packed, dense)
+        return (mean, members) if return_members else mean
+    if any(b.device != dense.device for b in packed.blobs):
+        raise ValueError(f"packed weights are on {packed.blobs[0].device} but "
+                         f"the rows are on {dense.device}")
+    x = dense.detach().float().contiguous()
+    res = ext.mlp_score_fused_ensemble(x, packed.blobs, packed.tables,
+                                       return_members, max_blocks, waves)
+    return (res[0], res[1]) if return_members else res[0]
+
+
+def attach_fused_ensemble(model) -> PackedEnsemble:
+    """Pack an EnsembleModel's members and route its predict() and
+    predict_members() through the fused ensemble path."""
+    packed = pack_ensemble(list(model.members))
+    model._fused_packed = packed
+    model.predict = lambda dense, cats=None: fused_ensemble_predict(packed, dense)
+    model.predict_members = lambda dense, cats=None: fused_ensemble_predict(
+        packed, dense, return_members=True)[1]
+    return packed

@@ -3507,6 +3507,9 @@ at::Tensor fm2_bwd(at::Tensor emb, at::Tensor s, at::Tensor dout, long F, long D
 at::Tensor mlp_score_fused(at::Tensor x, at::Tensor packed,
                            at::Tensor layer_table, int64_t max_blocks,
                            int64_t waves);
+std::vector<at::Tensor> mlp_score_fused_ensemble(
+    at::Tensor x, std::vector<at::Tensor> blobs, std::vector<at::Tensor> tables,
+    bool return_members, int64_t max_blocks, int64_t waves);
 
 // ---------------------------------------------------------------------------
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -3551,4 +3554,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("emb_adagrad_step", &emb_adagrad_step);
   m.def("mlp_score_fused", &mlp_score_fused, py::arg("x"), py::arg("packed_weights"),
         py::arg("layer_table"), py::arg("max_blocks") = 0, py::arg("waves") = 8);
+  m.def("mlp_score_fused_ensemble", &mlp_score_fused_ensemble, py::arg("x"),
+        py::arg("blobs"), py::arg("tables"), py::arg("return_members") = false,
+        py::arg("max_blocks") = 0, py::arg("waves") = 8);
 }

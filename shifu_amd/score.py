@@ -8,7 +8,11 @@ score per row, and optionally report AUC against the target column.
     python -m shifu_amd.score --model final_model/ \
         --data part-*.csv.gz --column-config ColumnConfig.json \
         --output scores.csv [--auc] [--batch 65536] [--device cpu|cuda]
-        [--fused off|on|auto]
+        [--fused off|on|auto] [--member-scores]
+
+--model also accepts a bagged model set (a directory with ensemble.json and
+model0/ .. modelN-1/, written by export_ensemble): the score is the members'
+mean, and --member-scores appends the N per-member scores to each line.
 
 Without --column-config the row layout is assumed to be the exported feature
 order (num_dense floats, then categorical ids) with no target/weight columns.
@@ -35,15 +39,22 @@ import numpy as np
 
 def score_files(model_dir: str, data_paths: List[str],
                 column_config: Optional[str] = None, batch: int = 65536,
-                device: str = "cpu", delimiter: str = "|", fused=False):
-    """Returns (scores np[N], targets np[N] or None).  fused: False | True |
-    "auto" — the single-kernel MLP scoring path (see load_exported)."""
+                device: str = "cpu", delimiter: str = "|", fused=False,
+                member_scores: bool = False):
+    """Returns (scores np[N], targets np[N] or None), and with
+    member_scores=True a third item, the per-member scores np[N, M] (M = 1
+    for a single bundle).  fused: False | True | "auto" — the single-kernel
+    MLP scoring path (see load_exported)."""
     import torch
-    from shifu_amd.train.export import load_exported
+    from shifu_amd.train.export import (ENSEMBLE_FILE, ensemble_member_dirs,
+                                        load_exported)
     from shifu_amd.io import load_csv_native
 
     model = load_exported(model_dir, device=device, fused=fused)
-    with open(f"{model_dir}/graph.json") as f:
+    spec_dir = model_dir
+    if os.path.exists(os.path.join(model_dir, ENSEMBLE_FILE)):
+        spec_dir = ensemble_member_dirs(model_dir)[0]
+    with open(f"{spec_dir}/graph.json") as f:
         spec = json.load(f)
     nd = int(spec["num_dense"])
     nc = len(spec.get("vocab_sizes", []))
@@ -71,22 +82,38 @@ def score_files(model_dir: str, data_paths: List[str],
         targets = None
 
     scores = np.empty(len(ds), dtype=np.float64)
+    n_members = len(getattr(model, "members", [None]))
+    members = np.empty((len(ds), n_members), dtype=np.float64) \
+        if member_scores else None
+    fp = getattr(model, "_fused_packed", None)
     with torch.no_grad():
         for s in range(0, len(ds), batch):
             e = min(s + batch, len(ds))
-            dense = torch.from_numpy(ds.dense[s:e]).to(device)
+            inputs = (torch.from_numpy(ds.dense[s:e]).to(device),)
             if nc:
-                cats = torch.from_numpy(ds.cats[s:e]).to(device)
-                p = model.predict(dense, cats)
+                inputs += (torch.from_numpy(ds.cats[s:e]).to(device),)
+            if member_scores and hasattr(fp, "group_sizes"):
+                # fused ensemble: mean and member columns from the same launches
+                from shifu_amd.ops.fused_mlp import fused_ensemble_predict
+                p, mem = fused_ensemble_predict(fp, inputs[0], return_members=True)
             else:
-                p = model.predict(dense)
+                p = model.predict(*inputs)
+                if member_scores:
+                    mem = (model.predict_members(*inputs)
+                           if hasattr(model, "predict_members")
+                           else p.reshape(-1, 1))
             scores[s:e] = p.cpu().numpy()
+            if member_scores:
+                members[s:e] = mem.float().cpu().numpy()
+    if member_scores:
+        return scores, targets, members
     return scores, targets
 
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser("shifu_amd.score", description=__doc__)
-    ap.add_argument("--model", required=True, help="export directory")
+    ap.add_argument("--model", required=True,
+                    help="export directory (a single bundle or an ensemble)")
     ap.add_argument("--data", required=True, nargs="+", help="csv(.gz) files/dirs")
     ap.add_argument("--column-config", default=None)
     ap.add_argument("--output", default="-", help="scores file ('-' = stdout); "
@@ -97,6 +124,9 @@ def main(argv=None) -> int:
     ap.add_argument("--fused", choices=["off", "on", "auto"], default="off",
                     help="single-kernel scoring for MLP bundles: 'on' errors "
                          "on an ineligible bundle, 'auto' keeps the layer path")
+    ap.add_argument("--member-scores", action="store_true",
+                    help="append the per-member scores of an ensemble to each "
+                         "output line (delimiter-separated, member order)")
     ap.add_argument("--auc", action="store_true",
                     help="also print AUC vs the target column (needs --column-config)")
     args = ap.parse_args(argv)
@@ -120,11 +150,18 @@ def main(argv=None) -> int:
     if world > 1 and args.device == "cuda":
         import torch
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", rank)))
-    scores, targets = (score_files(args.model, my_paths, args.column_config,
-                                   args.batch, args.device, args.delimiter,
-                                   fused={"off": False, "on": True,
-                                          "auto": "auto"}[args.fused])
-                       if my_paths else (np.empty(0), None))
+    members = None
+    if my_paths:
+        res = score_files(args.model, my_paths, args.column_config,
+                          args.batch, args.device, args.delimiter,
+                          fused={"off": False, "on": True,
+                                 "auto": "auto"}[args.fused],
+                          member_scores=args.member_scores)
+        scores, targets = res[0], res[1]
+        if args.member_scores:
+            members = res[2]
+    else:
+        scores, targets = np.empty(0), None
 
     if args.output == "-" and world == 1:
         out = sys.stdout
@@ -134,8 +171,13 @@ def main(argv=None) -> int:
              else f"scores.part{rank}")
         out = open(path, "w")
     try:
-        for v in scores:
-            out.write(f"{v:.6f}\n")
+        if members is None:
+            for v in scores:
+                out.write(f"{v:.6f}\n")
+        else:
+            for v, row in zip(scores, members):
+                out.write(args.delimiter.join(
+                    [f"{v:.6f}"] + [f"{c:.6f}" for c in row]) + "\n")
     finally:
         if out is not sys.stdout:
             out.close()

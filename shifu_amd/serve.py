@@ -35,6 +35,7 @@ class ShifuScorer:
         self.model: Optional[torch.nn.Module] = None
         self.num_dense = 0
         self.num_cat = 0
+        self.num_members = 1
         self.device = "cpu"
 
     def init(self, generic_model_config_path: str, device: str = "cpu",
@@ -49,6 +50,21 @@ class ShifuScorer:
             os.path.abspath(generic_model_config_path))
         if not os.path.isdir(model_path):
             model_path = os.path.dirname(os.path.abspath(generic_model_config_path))
+        # a bagged model set: ensemble.json under modelpath or beside the config
+        from shifu_amd.train.export import ENSEMBLE_FILE, ensemble_member_dirs
+        for d in (model_path,
+                  os.path.dirname(os.path.abspath(generic_model_config_path))):
+            if os.path.exists(os.path.join(d, ENSEMBLE_FILE)):
+                from shifu_amd.train.export import load_exported_ensemble
+                self.model = load_exported_ensemble(d, device=device, fused=fused)
+                self.device = device
+                with open(os.path.join(ensemble_member_dirs(d)[0],
+                                       "graph.json")) as f:
+                    spec = json.load(f)
+                self.num_dense = int(spec["num_dense"])
+                self.num_cat = len(spec.get("vocab_sizes", []))
+                self.num_members = len(self.model.members)
+                return
         gj = os.path.join(model_path, "graph.json")
         if os.path.exists(gj):
             from shifu_amd.train.export import load_exported
@@ -80,29 +96,56 @@ class ShifuScorer:
         self.model = _SavedModelGraph(self._pb_nodes)
         self.device = "cpu"
 
+    def _row_tensors(self, row: Sequence[float]):
+        arr = np.asarray(row, dtype=np.float64)
+        dense = torch.tensor(arr[:self.num_dense], dtype=torch.float32,
+                             device=self.device).reshape(1, -1)
+        if not self.num_cat:
+            return (dense,)
+        cats = torch.tensor(arr[self.num_dense:self.num_dense + self.num_cat],
+                            dtype=torch.int64, device=self.device).reshape(1, -1)
+        return dense, cats
+
+    def _predict_members(self, *inputs) -> "torch.Tensor":
+        """Per-member scores [B, M]; a single model is its own only member."""
+        if hasattr(self.model, "predict_members"):
+            return self.model.predict_members(*inputs)
+        return self.model.predict(*inputs).reshape(-1, 1)
+
     def compute(self, row: Sequence[float]) -> float:
         """Score one row: first num_dense values are normalized floats, the
         rest (if any) categorical ids.  Returns p in [0,1]."""
         if self.model is None:
             raise RuntimeError("scorer not initialized")
-        arr = np.asarray(row, dtype=np.float64)
-        dense = torch.tensor(arr[:self.num_dense], dtype=torch.float32,
-                             device=self.device).reshape(1, -1)
-        if self.num_cat:
-            cats = torch.tensor(arr[self.num_dense:self.num_dense + self.num_cat],
-                                dtype=torch.int64, device=self.device).reshape(1, -1)
-            p = self.model.predict(dense, cats)
-        else:
-            p = self.model.predict(dense)
+        p = self.model.predict(*self._row_tensors(row))
         return float(p.reshape(-1)[0])
 
-    def compute_batch(self, dense: np.ndarray, cats: Optional[np.ndarray] = None) -> np.ndarray:
+    def compute_members(self, row: Sequence[float]) -> list:
+        """The per-member scores of one row (compute() is their mean)."""
+        if self.model is None:
+            raise RuntimeError("scorer not initialized")
+        p = self._predict_members(*self._row_tensors(row))
+        return [float(v) for v in p.float().reshape(-1).cpu()]
+
+    def compute_batch(self, dense: np.ndarray, cats: Optional[np.ndarray] = None,
+                      return_members: bool = False):
+        """Scores np[B]; with return_members=True, (scores np[B], per-member
+        scores np[B, M])."""
         if self.model is None:
             raise RuntimeError("scorer not initialized")
         d = torch.tensor(np.asarray(dense, dtype=np.float32), device=self.device)
         if cats is not None and self.num_cat:
-            c = torch.tensor(np.asarray(cats, dtype=np.int64), device=self.device)
-            p = self.model.predict(d, c)
+            inputs = (d, torch.tensor(np.asarray(cats, dtype=np.int64),
+                                      device=self.device))
         else:
-            p = self.model.predict(d)
-        return p.cpu().numpy()
+            inputs = (d,)
+        if not return_members:
+            return self.model.predict(*inputs).cpu().numpy()
+        fp = getattr(self.model, "_fused_packed", None)
+        if fp is not None and hasattr(fp, "group_sizes"):
+            # fused ensemble: mean and member columns from the same launches
+            from shifu_amd.ops.fused_mlp import fused_ensemble_predict
+            p, mem = fused_ensemble_predict(fp, d, return_members=True)
+        else:
+            p, mem = self.model.predict(*inputs), self._predict_members(*inputs)
+        return p.cpu().numpy(), mem.float().cpu().numpy()

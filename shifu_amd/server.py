@@ -3,7 +3,9 @@
 The reference's scoring side is a Java `Computable` embedded in the Shifu
 eval pipeline (TensorflowModel.java).  This module adds the standalone
 deployment shape: a FastAPI service that loads the same export layout
-(GenericModelConfig.json + graph.json + weights) and scores rows.
+(GenericModelConfig.json + graph.json + weights) and scores rows.  --model may
+also be a bagged model set (ensemble.json + model0/ .. modelN-1/): /score then
+returns the members' mean and /health reports how many members there are.
 
     python -m shifu_amd.server --model final_model/ --port 8800
     POST /score        {"rows": [[...], ...]}   -> {"scores": [...]}
@@ -39,7 +41,8 @@ def create_app(model_dir: str, device: str = "cpu"):
     @app.get("/health")
     def health():
         return {"status": "ok", "num_dense": scorer.num_dense,
-                "num_cat": scorer.num_cat, "device": device}
+                "num_cat": scorer.num_cat, "device": device,
+                "members": scorer.num_members}
 
     @app.post("/score")
     def score(req: Rows):

@@ -119,6 +119,80 @@ def export_model(model: torch.nn.Module, final_model_path: str,
     return final_model_path
 
 
+ENSEMBLE_FILE = "ensemble.json"
+
+
+def export_ensemble(models: Sequence[torch.nn.Module], final_model_path: str,
+                    model_name: str = "model", algorithm: str = "NN",
+                    selected_columns: Optional[Sequence[int]] = None) -> str:
+    """Write a bagged model set: `model{i}/` ordinary export_model bundles,
+    `ensemble.json` naming them in member order, and a top-level
+    GenericModelConfig.json; returns the directory."""
+    from shifu_amd.models.ensemble import EnsembleModel
+    models = list(models)
+    EnsembleModel(models)           # members must agree on the row layout
+    os.makedirs(final_model_path, exist_ok=True)
+    names = [f"model{i}" for i in range(len(models))]
+    for name, m in zip(names, models):
+        export_model(m, os.path.join(final_model_path, name),
+                     model_name=model_name, algorithm=algorithm,
+                     selected_columns=selected_columns)
+    with open(os.path.join(final_model_path, ENSEMBLE_FILE), "w") as f:
+        json.dump({"family": "ensemble", "combine": "mean", "members": names},
+                  f, indent=2)
+    gmc = {
+        "inputnames": ["shifu_input_0"],
+        "properties": {"algorithm": algorithm, "tags": ["serve"],
+                       "normtype": "ZSCALE", "weightsfile": ENSEMBLE_FILE},
+        "outputnames": ["shifu_output_0"],
+        "modelpath": os.path.abspath(final_model_path),
+    }
+    if selected_columns is not None:
+        gmc["properties"]["selectedcolumns"] = list(selected_columns)
+    with open(os.path.join(final_model_path, "GenericModelConfig.json"), "w") as f:
+        json.dump(gmc, f, indent=2)
+    return final_model_path
+
+
+def ensemble_member_dirs(final_model_path: str) -> List[str]:
+    """Member bundle directories of an ensemble directory, in member order."""
+    with open(os.path.join(final_model_path, ENSEMBLE_FILE)) as f:
+        spec = json.load(f)
+    if spec.get("family") != "ensemble" or spec.get("combine", "mean") != "mean":
+        raise ValueError(f"{final_model_path}: unsupported {ENSEMBLE_FILE} "
+                         f"(family={spec.get('family')!r}, "
+                         f"combine={spec.get('combine')!r})")
+    if not spec.get("members"):
+        raise ValueError(f"{final_model_path}: {ENSEMBLE_FILE} lists no members")
+    return [os.path.join(final_model_path, m) for m in spec["members"]]
+
+
+def load_exported_ensemble(final_model_path: str, device: str = "cpu",
+                           fused=False) -> torch.nn.Module:
+    """Reconstruct an exported bagged model set as an EnsembleModel.
+
+    fused follows load_exported: True routes predict() through the fused
+    ensemble kernel (ops/fused_mlp.py) and raises ValueError with
+    ensemble_eligible's reason when the members do not qualify; "auto"
+    quietly keeps the layer path there; False never touches the fused path."""
+    if fused not in (False, True, "auto"):
+        raise ValueError(f"fused must be False, True or 'auto', got {fused!r}")
+    from shifu_amd.models.ensemble import EnsembleModel
+    members = [load_exported(d, device=device, fused=False)
+               for d in ensemble_member_dirs(final_model_path)]
+    model = EnsembleModel(members).to(device).eval()
+    if fused:
+        from shifu_amd.ops.fused_mlp import (attach_fused_ensemble,
+                                             ensemble_eligible)
+        ok, why = ensemble_eligible(members)
+        if ok:
+            attach_fused_ensemble(model)
+        elif fused is True:
+            raise ValueError(f"{final_model_path}: fused scoring unavailable "
+                             f"for this ensemble: {why}")
+    return model
+
+
 def load_exported(final_model_path: str, device: str = "cpu",
                   fused=False) -> torch.nn.Module:
     """Reconstruct an exported model from graph.json + weights (the scorer path).
@@ -129,6 +203,8 @@ def load_exported(final_model_path: str, device: str = "cpu",
     path there; fused=False (default) never touches the fused path."""
     if fused not in (False, True, "auto"):
         raise ValueError(f"fused must be False, True or 'auto', got {fused!r}")
+    if os.path.exists(os.path.join(final_model_path, ENSEMBLE_FILE)):
+        return load_exported_ensemble(final_model_path, device=device, fused=fused)
     from shifu_amd.models.mlp import ShifuMLP
     from shifu_amd.models.wide_deep import WideDeep
     from shifu_amd.models.deepfm import DeepFM

@@ -15,10 +15,13 @@ serves (TrainParams default [50, 50] tanh):
 
 --fused routes an MLP bundle through the single-kernel scoring path
 (shifu_amd/ops/fused_mlp.py); without it the per-layer kernels run.
+--ensemble M (with --family mlp) scores a bagged set of M such nets (seeds
+11 .. 11+M-1, exported with export_ensemble); every line then carries "members".
 
 Synthetic model + data (no network).  One JSON line per mode.
 Usage: python tools/score_bench.py [--device cuda] [--batch 65536]
-                                   [--family mlp [--fused] [--hidden 50,50]]
+                                   [--family mlp [--fused] [--hidden 50,50]
+                                    [--ensemble M]]
 """
 import argparse
 import json
@@ -33,7 +36,8 @@ import numpy as np
 import torch
 
 
-def _predict_device_time(sc, dense, batch, repeats, fused, model_desc):
+def _predict_device_time(sc, dense, batch, repeats, fused, model_desc,
+                         extra):
     """Device time of model.predict on one resident batch: HIP events around
     predict alone, one warm-up, median of `repeats`."""
     x = torch.tensor(dense[:batch], device="cuda")
@@ -56,7 +60,7 @@ def _predict_device_time(sc, dense, batch, repeats, fused, model_desc):
         "repeats": repeats, "min_us": times[0], "max_us": times[-1],
         "input_gb_per_s": x.numel() * 4 / (med * 1e-6) / 1e9,
         "higher_is_better": False, "fused": fused,
-        "config": {"model": model_desc}}), flush=True)
+        "config": {"model": model_desc}, **extra}), flush=True)
 
 
 def main():
@@ -73,23 +77,34 @@ def main():
                     help="--family mlp: hidden layer widths (tanh)")
     ap.add_argument("--fused", action="store_true",
                     help="--family mlp: single-kernel scoring path")
+    ap.add_argument("--ensemble", type=int, default=0, metavar="M",
+                    help="--family mlp: a bagged set of M members (mean score)")
     ap.add_argument("--repeats", type=int, default=30,
                     help="--family mlp --device cuda: predict() timing repeats")
     args = ap.parse_args()
 
     from shifu_amd.models.wide_deep import WideDeep
     from shifu_amd.models.mlp import ShifuMLP
-    from shifu_amd.train.export import export_model
+    from shifu_amd.train.export import export_ensemble, export_model
     from shifu_amd.serve import ShifuScorer
 
     mlp = args.family == "mlp"
     if args.fused and not mlp:
         ap.error("--fused needs --family mlp")
+    if args.ensemble and not mlp:
+        ap.error("--ensemble needs --family mlp")
+    if args.ensemble < 0:
+        ap.error("--ensemble must be >= 1")
+    extra = {"members": args.ensemble} if args.ensemble else {}
     torch.manual_seed(11)
     if mlp:
         hidden = [int(h) for h in args.hidden.split(",") if h]
         model = ShifuMLP(args.n_dense, hidden, ["tanh"] * len(hidden), seed=11)
         model_desc = f"mlp[{args.n_dense}dense,hidden{hidden}]"
+        if args.ensemble:
+            members = [ShifuMLP(args.n_dense, hidden, ["tanh"] * len(hidden),
+                                seed=11 + i) for i in range(args.ensemble)]
+            model_desc = f"{args.ensemble}x{model_desc}"
     else:
         model = WideDeep(args.n_dense, [args.vocab] * args.n_cat, args.embed_dim,
                          [1024, 512, 256], ["relu"] * 3, seed=11)
@@ -97,7 +112,10 @@ def main():
                       f"*{args.embed_dim}d+{args.n_dense}dense,"
                       f"tower[1024, 512, 256]]")
     with tempfile.TemporaryDirectory() as td:
-        export_model(model, td)
+        if args.ensemble:
+            export_ensemble(members, td)
+        else:
+            export_model(model, td)
         sc = ShifuScorer()
         sc.init(os.path.join(td, "GenericModelConfig.json"),
                 device=args.device, fused=args.fused)
@@ -130,7 +148,7 @@ def main():
             "mode": "compute_batch", "device": args.device,
             "batch": args.batch, "rows": n, "data": "synthetic",
             "fused": args.fused,
-            "config": {"model": model_desc}}), flush=True)
+            "config": {"model": model_desc}, **extra}), flush=True)
 
         # per-row latency (Java Computable call pattern)
         k = 2000
@@ -146,11 +164,11 @@ def main():
             "metric": "scoring_row_latency_us", "value": dt / k * 1e6,
             "unit": "us/row", "mode": "compute", "device": args.device,
             "rows": k, "higher_is_better": False,
-            "fused": args.fused}), flush=True)
+            "fused": args.fused, **extra}), flush=True)
 
         if mlp and args.device == "cuda":
             _predict_device_time(sc, dense, args.batch, args.repeats,
-                                 args.fused, model_desc)
+                                 args.fused, model_desc, extra)
 
 
 if __name__ == "__main__":
