@@ -574,6 +574,21 @@ DEVINL void xcd_swizzle_xy(int& bx, int& by, int on) {
   by = lin2 / gx;
 }
 
+// Wide-epilogue B row order (PERM): LDS row p of a wave's 64-row strip
+// (fragment nf = p>>4, fragment-row i = p&15) holds operand row
+// (i>>2)*16 + nf*4 + (i&3) of that strip.  With the MFMA operands swapped
+// (accumulator lane (r16,kgrp) = output row r16, fragment-rows kgrp*4+r) a
+// lane then owns, across nf = 0..3, the 16 CONTIGUOUS output columns
+// kgrp*16 .. kgrp*16+15.  The permutation stays inside each aligned group of
+// 64 rows and only picks the SOURCE row; the LDS image, its swizzle
+// (keyed on the LDS row) and the fragment reads are unchanged.
+template <bool PERM>
+DEVINL int v4_src_row(int p) {
+  if (!PERM) return p;
+  return (p & ~63) | (((p >> 2) & 3) << 4) | (((p >> 4) & 3) << 2) | (p & 3);
+}
+
+template <bool PERM = false>
 DEVINL void v4_stage_half_glds(const bf16* __restrict__ P, char* lds_region,
                                int R0, int half, int k0, int K, int tid) {
   // one 16KB half (rows half*128..+127 of the 256-row region), 2 glds/thread
@@ -584,12 +599,14 @@ DEVINL void v4_stage_half_glds(const bf16* __restrict__ P, char* lds_region,
     int row = byte >> 7;               // within half
     int g = (byte >> 4) & 7;
     int gsrc = g ^ (row & 7);          // swizzle on the SOURCE address
-    const bf16* src = P + (long)(R0 + half * 128 + row) * K + k0 + gsrc * 8;
+    const bf16* src = P + (long)(R0 + half * 128 + v4_src_row<PERM>(row)) * K +
+                      k0 + gsrc * 8;
     char* dst = lds_region + half * 16384 + c * 8192 + wave * 1024;
     __builtin_amdgcn_global_load_lds((gas_ptr)src, (las_ptr)dst, 16, 0, 0);
   }
 }
 
+template <bool PERM = false>
 DEVINL void v4_stage_half_guarded(const bf16* __restrict__ P, char* lds_region,
                                   int R0, int half, int k0, int RM, int K, int tid) {
   // same image via guarded loads + ds_writes (edge tiles); 2 chunks/thread
@@ -599,7 +616,7 @@ DEVINL void v4_stage_half_guarded(const bf16* __restrict__ P, char* lds_region,
     int row = byte >> 7;
     int g = (byte >> 4) & 7;
     int gsrc = g ^ (row & 7);
-    int grow = R0 + half * 128 + row;
+    int grow = R0 + half * 128 + v4_src_row<PERM>(row);
     long gk = (long)k0 + gsrc * 8;
     s16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
     if (grow < RM) {
@@ -613,6 +630,8 @@ DEVINL void v4_stage_half_guarded(const bf16* __restrict__ P, char* lds_region,
 }
 
 // stage one slot: slot 0/1 = A half0/1, slot 2/3 = B half0/1, of k-tile kt
+// (BPERM: B rows in the wide-epilogue order, see v4_src_row)
+template <bool BPERM = false>
 DEVINL void v4_stage_slot(const bf16* A, const bf16* B, char* smem, int slot,
                           int kt, int m0, int n0, int M, int N, int K, int tid) {
   int k0 = kt * V4_BK;
@@ -624,8 +643,67 @@ DEVINL void v4_stage_slot(const bf16* A, const bf16* B, char* smem, int slot,
     else v4_stage_half_guarded(A, smem + V4_A(par), m0, slot, k0, M, K, tid);
   } else {
     bool full = full_k && (n0 + V4_BN <= N);
-    if (full) v4_stage_half_glds(B, smem + V4_B(par), n0, slot - 2, k0, K, tid);
-    else v4_stage_half_guarded(B, smem + V4_B(par), n0, slot - 2, k0, N, K, tid);
+    if (full) v4_stage_half_glds<BPERM>(B, smem + V4_B(par), n0, slot - 2, k0, K, tid);
+    else v4_stage_half_guarded<BPERM>(B, smem + V4_B(par), n0, slot - 2, k0, N, K, tid);
+  }
+}
+
+// Rows of the wide epilogue (see gemm_nt_v4_kernel, WIDE): per mf the lane
+// owns output row row0 + mf*16 and columns cbase..cbase+15, value nf*4+r =
+// acc[mf][nf][r].  FULL: all 16 columns go out as 16 B chunks, no column
+// guards.  Otherwise each chunk is a wide store only when vec_ok and wholly
+// below N, else a per-element loop (any N; atomicAdd when `atomic`).
+// ACT >= 0 fixes the activation at compile time; ACT < 0 reads `act`.
+template <int EPI, typename OUT_T, int ACT, bool FULL>
+DEVINL void v4_wide_rows(const f32x4 (&acc)[8][4], const float (&bw)[16],
+                         OUT_T* Cz, int row0, int M, int N, int cbase, int act,
+                         bool vec_ok, bool atomic) {
+  constexpr int CH = (EPI == EPI_F32) ? 4 : 8;   // columns per 16 B chunk
+#pragma unroll
+  for (int mf = 0; mf < 8; ++mf) {
+    const int row = row0 + mf * 16;
+    if (row >= M) continue;
+    float v[16];
+#pragma unroll
+    for (int nf = 0; nf < 4; ++nf)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float x = acc[mf][nf][r];
+        if (EPI == EPI_BIAS_ACT)
+          x = act_fwd(x + bw[nf * 4 + r], ACT >= 0 ? ACT : act);
+        v[nf * 4 + r] = x;
+      }
+    OUT_T* crow = Cz + (long)row * N;
+#pragma unroll
+    for (int ch = 0; ch < 16 / CH; ++ch) {
+      const int cb = cbase + ch * CH;
+      if (FULL || (vec_ok && cb + CH <= N)) {
+        if (EPI == EPI_F32) {
+          *(f32x4*)((float*)crow + cb) =
+              f32x4{v[ch * 4], v[ch * 4 + 1], v[ch * 4 + 2], v[ch * 4 + 3]};
+        } else {
+          s16x8 pk;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            bf16 t = __float2bfloat16(v[ch * CH + j]);
+            pk[j] = *(const short*)&t;
+          }
+          *(s16x8*)((bf16*)crow + cb) = pk;
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < CH; ++j) {
+          if (cb + j >= N) continue;
+          float x = v[ch * CH + j];
+          if (EPI == EPI_F32) {
+            if (atomic) atomicAdd((float*)crow + cb + j, x);
+            else ((float*)crow)[cb + j] = x;
+          } else {
+            ((bf16*)crow)[cb + j] = __float2bfloat16(x);
+          }
+        }
+      }
+    }
   }
 }
 
@@ -633,7 +711,16 @@ DEVINL void v4_stage_slot(const bf16* A, const bf16* B, char* smem, int slot,
 // VAR 1: q1's phase barrier merges into the boundary one (2 barriers/tile);
 //        safe: every region staged right after the merged barrier had its
 //        last reads completed by the lgkmcnt(0) preceding it
-template <int EPI, typename OUT_T, bool SPLITK = false, int VAR = 0>
+// WIDE 1: wide-store epilogue.  The MFMA operand roles are swapped
+//        (acc = B-fragment x A-fragment, so each accumulator fragment is the
+//        transposed 16x16 block) and B is staged in v4_src_row order: lane
+//        (r16,kgrp) then holds, per mf, output row mf*16+r16 and the 16
+//        contiguous columns kgrp*16..+15 of the wave's strip, stored as
+//        2 x 16 B (bf16) or 4 x 16 B (f32) instead of 16 scalar stores.
+//        Same products in the same K order per element as WIDE 0.
+// WIDE 0: the original column-per-lane accumulator layout and per-element
+//        epilogue (SHIFU_GEMM_EPI=narrow).
+template <int EPI, typename OUT_T, bool SPLITK = false, int VAR = 0, bool WIDE = true>
 __global__ __launch_bounds__(512, 1)
 void gemm_nt_v4_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
                        OUT_T* __restrict__ C, const bf16* __restrict__ bias,
@@ -670,13 +757,13 @@ void gemm_nt_v4_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
 
   // prologue: A(t0), B(t0), B(t1) fully; then enter the loop which stages
   // A(t+1) in phases 0-1 and B(t+2) in phases 1-2 of each tile t.
-  v4_stage_slot(A, B, smem, 0, kt_lo, m0, n0, M, N, K, tid);
-  v4_stage_slot(A, B, smem, 1, kt_lo, m0, n0, M, N, K, tid);
-  v4_stage_slot(A, B, smem, 2, kt_lo, m0, n0, M, N, K, tid);
-  v4_stage_slot(A, B, smem, 3, kt_lo, m0, n0, M, N, K, tid);
+  v4_stage_slot<WIDE>(A, B, smem, 0, kt_lo, m0, n0, M, N, K, tid);
+  v4_stage_slot<WIDE>(A, B, smem, 1, kt_lo, m0, n0, M, N, K, tid);
+  v4_stage_slot<WIDE>(A, B, smem, 2, kt_lo, m0, n0, M, N, K, tid);
+  v4_stage_slot<WIDE>(A, B, smem, 3, kt_lo, m0, n0, M, N, K, tid);
   if (n_kt > 1) {
-    v4_stage_slot(A, B, smem, 2, kt_lo + 1, m0, n0, M, N, K, tid);
-    v4_stage_slot(A, B, smem, 3, kt_lo + 1, m0, n0, M, N, K, tid);
+    v4_stage_slot<WIDE>(A, B, smem, 2, kt_lo + 1, m0, n0, M, N, K, tid);
+    v4_stage_slot<WIDE>(A, B, smem, 3, kt_lo + 1, m0, n0, M, N, K, tid);
   }
   {
     bool b1_glds = (n_kt > 1) && ((kt_lo + 1) * V4_BK + V4_BK <= K) &&
@@ -717,12 +804,12 @@ void gemm_nt_v4_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
         }
       // stage schedule: q0 -> A halves (t+1); q1 -> B halves (t+2)
       if (q == 0 && t + 1 < n_kt) {
-        v4_stage_slot(A, B, smem, 0, kt + 1, m0, n0, M, N, K, tid);
-        v4_stage_slot(A, B, smem, 1, kt + 1, m0, n0, M, N, K, tid);
+        v4_stage_slot<WIDE>(A, B, smem, 0, kt + 1, m0, n0, M, N, K, tid);
+        v4_stage_slot<WIDE>(A, B, smem, 1, kt + 1, m0, n0, M, N, K, tid);
       }
       if (q == 1 && t + 2 < n_kt) {
-        v4_stage_slot(A, B, smem, 2, kt + 2, m0, n0, M, N, K, tid);
-        v4_stage_slot(A, B, smem, 3, kt + 2, m0, n0, M, N, K, tid);
+        v4_stage_slot<WIDE>(A, B, smem, 2, kt + 2, m0, n0, M, N, K, tid);
+        v4_stage_slot<WIDE>(A, B, smem, 3, kt + 2, m0, n0, M, N, K, tid);
       }
 
       __builtin_amdgcn_s_setprio(1);
@@ -732,8 +819,11 @@ void gemm_nt_v4_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
         for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
           for (int nf = 0; nf < 4; ++nf)
-            acc[q * 4 + m2][nf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                afr[m2][ks], bfr[nf][ks], acc[q * 4 + m2][nf], 0, 0, 0);
+            acc[q * 4 + m2][nf] = WIDE
+                ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                      bfr[nf][ks], afr[m2][ks], acc[q * 4 + m2][nf], 0, 0, 0)
+                : __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                      afr[m2][ks], bfr[nf][ks], acc[q * 4 + m2][nf], 0, 0, 0);
       __builtin_amdgcn_s_setprio(0);
       // phase barrier: bound wave skew so the next phase's staging never
       // overwrites a region a lagging wave still reads.  lgkmcnt(0) flushes
@@ -754,7 +844,66 @@ void gemm_nt_v4_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
     __builtin_amdgcn_s_barrier();
   }
 
-  // epilogue (bias hoisted: 4 loads per lane, not 32)
+  if (WIDE) {
+    // wide epilogue: per mf this lane owns output row mf*16+r16 and columns
+    // cbase..cbase+15 (value nf*4+r = acc[mf][nf][r]).  A chunk of 8 bf16
+    // (4 f32) columns goes out as one 16 B store when it lies wholly below N
+    // and every row start keeps it 16 B aligned (N % 8 resp. N % 4 == 0 and
+    // an aligned base); any other chunk takes the per-element loop, which is
+    // correct for any N.  Atomic split-K keeps per-element atomicAdd.
+    const int cbase = n0 + wn * 64 + kgrp * 16;
+    OUT_T* Cz = C;
+    if (SPLITK) Cz += (long)blockIdx.z * slab;
+    constexpr int CH = (EPI == EPI_F32) ? 4 : 8;   // columns per 16 B chunk
+    const bool vec_ok = (N % CH == 0) && (((size_t)Cz & 15) == 0) &&
+                        !(SPLITK && slab == 0);
+    float bw[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) bw[j] = 0.f;
+    if (EPI == EPI_BIAS_ACT) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int cb = cbase + h * 8;
+        if (cb + 8 <= N && (((size_t)(bias + cb)) & 15) == 0) {
+          s16x8 raw = *(const s16x8*)(bias + cb);
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            bw[h * 8 + j] = __uint_as_float((unsigned)(unsigned short)raw[j] << 16);
+        } else {
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            if (cb + j < N) bw[h * 8 + j] = __bfloat162float(bias[cb + j]);
+        }
+      }
+    }
+    const int row0 = m0 + wm * 128 + r16;
+    const bool atomic = SPLITK && slab == 0;
+    if (vec_ok && cbase + 16 <= N) {
+      // every chunk of this lane is a wide store: straight-line rows with
+      // the activation resolved once per kernel, not once per element
+      if (EPI == EPI_BIAS_ACT) {
+        switch (act) {
+          case ACT_SIGMOID:
+            v4_wide_rows<EPI, OUT_T, ACT_SIGMOID, true>(acc, bw, Cz, row0, M, N, cbase, act, true, atomic); break;
+          case ACT_TANH:
+            v4_wide_rows<EPI, OUT_T, ACT_TANH, true>(acc, bw, Cz, row0, M, N, cbase, act, true, atomic); break;
+          case ACT_RELU:
+            v4_wide_rows<EPI, OUT_T, ACT_RELU, true>(acc, bw, Cz, row0, M, N, cbase, act, true, atomic); break;
+          case ACT_LEAKY:
+            v4_wide_rows<EPI, OUT_T, ACT_LEAKY, true>(acc, bw, Cz, row0, M, N, cbase, act, true, atomic); break;
+          default:
+            v4_wide_rows<EPI, OUT_T, ACT_NONE, true>(acc, bw, Cz, row0, M, N, cbase, act, true, atomic); break;
+        }
+      } else {
+        v4_wide_rows<EPI, OUT_T, ACT_NONE, true>(acc, bw, Cz, row0, M, N, cbase, act, true, atomic);
+      }
+    } else {
+      v4_wide_rows<EPI, OUT_T, -1, false>(acc, bw, Cz, row0, M, N, cbase, act, vec_ok, atomic);
+    }
+    return;
+  }
+
+  // narrow epilogue (bias hoisted: 4 loads per lane, not 32)
   float bvs[4] = {0.f, 0.f, 0.f, 0.f};
   if (EPI == EPI_BIAS_ACT) {
 #pragma unroll
@@ -1231,6 +1380,17 @@ static int gemm_impl() {
   return v;
 }
 
+// v4/v4b epilogue selector (SHIFU_GEMM_EPI):
+//   wide   — swapped-operand accumulator layout, 16 B row stores (default)
+//   narrow — the original per-element epilogue (A/B from one build)
+static bool gemm_epi_wide() {
+  static int v = [] {
+    const char* e = getenv("SHIFU_GEMM_EPI");
+    return (e && !strcmp(e, "narrow")) ? 0 : 1;
+  }();
+  return v != 0;
+}
+
 // launch whichever 256^2 kernel the selector picks (typed, so the argument
 // marshalling stays hipLaunchKernelGGL's)
 static int xcd_swz_on() {
@@ -1254,7 +1414,15 @@ static void launch_256(dim3 grid, const bf16* A, const bf16* B, OUT_T* C,
     hipLaunchKernelGGL((KERN), grid, dim3(512), V4_LDS_BYTES, s,            \
                        A, B, C, bias, M, N, K, act, slab, swz);             \
   } while (0)
-  switch (gemm_impl()) {
+  const int impl = gemm_impl();
+  if (!gemm_epi_wide() && (impl == GI_V4 || impl == GI_V4B)) {
+    if (impl == GI_V4B)
+      SHIFU_LAUNCH_256((gemm_nt_v4_kernel<EPI, OUT_T, SPLITK, 1, false>));
+    else
+      SHIFU_LAUNCH_256((gemm_nt_v4_kernel<EPI, OUT_T, SPLITK, 0, false>));
+    return;
+  }
+  switch (impl) {
     case GI_V4B: SHIFU_LAUNCH_256((gemm_nt_v4_kernel<EPI, OUT_T, SPLITK, 1>)); break;
     case GI_V5:  SHIFU_LAUNCH_256((gemm_nt_v5_kernel<EPI, OUT_T, SPLITK, 0>)); break;
     case GI_V5B: SHIFU_LAUNCH_256((gemm_nt_v5_kernel<EPI, OUT_T, SPLITK, 1>)); break;
