@@ -2755,7 +2755,7 @@ __global__ void emb_scatter_kernel(bf16* __restrict__ arena, const long* __restr
   long total = n * (pairs ? pairs : 1);
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   long stride = (long)gridDim.x * blockDim.x;
-  if (pairs) {
+  if (pairs && !(D & 1)) {
     for (long t = i; t < total; t += stride) {
       long e = t / pairs, dp = t % pairs;
       float sc = scale * (rowscale ? rowscale[e] : 1.0f);
@@ -2765,12 +2765,19 @@ __global__ void emb_scatter_kernel(bf16* __restrict__ arena, const long* __restr
       add.y = __float2bfloat16(sc * __bfloat162float(vals[e * D + dp * 2 + 1]));
       unsafeAtomicAdd((__hip_bfloat162*)(arena + row * D + dp * 2), add);
     }
-    if (D & 1) {  // odd tail element
-      for (long e = i; e < n; e += stride) {
-        float sc = scale * (rowscale ? rowscale[e] : 1.0f);
-        atomic_add_bf16_scalar(arena + rows[e] * D + D - 1,
-                               sc * __bfloat162float(vals[e * D + D - 1]));
-      }
+  } else if (pairs) {
+    // odd D > 1 (cold path): row*D is odd for every odd row, so a packed
+    // atomic at row*D + dp*2 would sit on a 2-byte boundary.  Every element
+    // goes through the CAS helper instead, which realigns to the containing
+    // 4-byte word.  A word that straddles two rows can be hit by CAS from
+    // both; and a CAS and a packed add on one word would also compose — both
+    // are 32-bit atomics on the same aligned word.
+    long tot = n * D;
+    for (long t = i; t < tot; t += stride) {
+      long e = t / D, d = t % D;
+      float sc = scale * (rowscale ? rowscale[e] : 1.0f);
+      atomic_add_bf16_scalar(arena + rows[e] * D + d,
+                             sc * __bfloat162float(vals[e * D + d]));
     }
   } else {  // D == 1
     for (long e = i; e < n; e += stride) {
@@ -2790,7 +2797,7 @@ __global__ void emb_scatter_acc_kernel(bf16* __restrict__ arena, const long* __r
   long total = n * (pairs ? pairs : 1);
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   long stride = (long)gridDim.x * blockDim.x;
-  if (pairs) {
+  if (pairs && !(D & 1)) {
     for (long t = i; t < total; t += stride) {
       long e = t / pairs, dp = t % pairs;
       long row = rows[e];
@@ -2800,13 +2807,16 @@ __global__ void emb_scatter_acc_kernel(bf16* __restrict__ arena, const long* __r
       add.y = __float2bfloat16(sc * __bfloat162float(vals[e * D + dp * 2 + 1]));
       unsafeAtomicAdd((__hip_bfloat162*)(arena + row * D + dp * 2), add);
     }
-    if (D & 1) {
-      for (long e = i; e < n; e += stride) {
-        long row = rows[e];
-        float sc = scale / (sqrtf(acc[row]) + eps);
-        atomic_add_bf16_scalar(arena + row * D + D - 1,
-                               sc * __bfloat162float(vals[e * D + D - 1]));
-      }
+  } else if (pairs) {
+    // odd D > 1: all elements through the word-realigning CAS helper (see
+    // emb_scatter_kernel — odd rows start on a 2-byte boundary)
+    long tot = n * D;
+    for (long t = i; t < tot; t += stride) {
+      long e = t / D, d = t % D;
+      long row = rows[e];
+      float sc = scale / (sqrtf(acc[row]) + eps);
+      atomic_add_bf16_scalar(arena + row * D + d,
+                             sc * __bfloat162float(vals[e * D + d]));
     }
   } else {
     for (long e = i; e < n; e += stride) {

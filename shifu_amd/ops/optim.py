@@ -145,7 +145,8 @@ class FusedOptimizer:
                 vf = vals.float()
                 rowsq = (vf * vf).mean(dim=1)
                 acc.index_add_(0, rows, rowsq)
-                denom = acc[rows].add(self.eps).sqrt_().unsqueeze(1)
+                # sqrt(acc) + eps, as the HIP kernels place it
+                denom = acc[rows].sqrt().add_(self.eps).unsqueeze(1)
                 p.data.index_add_(0, rows, (-self.emb_lr * vf / denom).to(p.dtype))
         else:  # sgd
             if p.dtype == torch.bfloat16 and use_hip(p):
@@ -176,7 +177,7 @@ class FusedOptimizer:
             if adagrad:
                 acc = p.data[:, D + 2]          # fp32 arena: plain f32 col
                 acc.index_add_(0, rows, gsq / DP)
-                denom = acc[rows].add(self.eps).sqrt_().unsqueeze(1)
+                denom = acc[rows].sqrt().add_(self.eps).unsqueeze(1)
                 upd[:, :D + 1] = -self.emb_lr * vf[:, :D + 1] / denom
             else:
                 upd[:, :D + 1] = -self.emb_lr * vf[:, :D + 1]

@@ -383,7 +383,8 @@ def test_embedding_gather_gpu():
     out = hip_ops().embedding_gather(arena, ids)
     ref = arena.float().index_select(0, ids.reshape(-1)).reshape(37, 4 * 64)
     assert torch.allclose(out.float(), ref, atol=1e-6)
-    # odd D (scalar path)
+    # D % 8 != 0 (scalar path; D=6 is even -- odd D is covered in
+    # test_embedding_kernels_gpu.py)
     arena2 = _rand_bf16(100, 6, seed=21)
     out2 = hip_ops().embedding_gather(arena2, ids % 100)
     ref2 = arena2.float().index_select(0, (ids % 100).reshape(-1)).reshape(37, 4 * 6)
