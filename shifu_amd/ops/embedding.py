@@ -119,7 +119,8 @@ class _UnifiedGatherFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, arena: torch.Tensor, flat_ids: torch.Tensor,
-                dense: torch.Tensor, F: int, D: int, defer: bool = False):
+                dense: torch.Tensor, F: int, D: int, defer: bool = False,
+                spans: torch.Tensor = None):
         B, nd = dense.shape
         hip = (arena.dtype == torch.bfloat16 and use_hip(arena)
                and D % 8 == 0 and dense.dtype == torch.bfloat16
@@ -141,6 +142,7 @@ class _UnifiedGatherFn(torch.autograd.Function):
         ctx.meta = (arena.shape, arena.dtype, F, D, nd)
         ctx.defer = bool(defer) and hip
         ctx.arena_ref = arena if ctx.defer else None
+        ctx.spans = spans
         return out, wide
 
     @staticmethod
@@ -159,16 +161,20 @@ class _UnifiedGatherFn(torch.autograd.Function):
             if lst is None:
                 lst = []
                 ctx.arena_ref._unified_grads = lst
+            # spans: host [F, 2] row range of every feature's table.  Entry
+            # (b, f) of flat_ids always lies in spans[f], which lets the
+            # optimizer take the once-hit fused update
+            # (ops/hip emb_update_unified_spans)
             lst.append((flat_ids.reshape(-1), dout, nd, dwide.contiguous(),
-                        F, D))
-            return None, None, None, None, None, None
+                        F, D, ctx.spans))
+            return None, None, None, None, None, None, None
         vals = torch.empty(n, DP, dtype=dtype, device=dout.device)
         v3 = vals.view(B, F, DP)
         v3[:, :, :D] = dout[:, nd:].reshape(B, F, D)
         v3[:, :, D] = dwide.to(dtype)
         v3[:, :, D + 1:] = 0
         grad = torch.sparse_coo_tensor(flat_ids.reshape(1, n), vals, shape)
-        return grad, None, None, None, None, None
+        return grad, None, None, None, None, None, None
 
 
 class UnifiedMultiEmbedding(torch.nn.Module):
@@ -205,6 +211,12 @@ class UnifiedMultiEmbedding(torch.nn.Module):
         self.register_buffer("offsets", offsets, persistent=False)
         self.register_buffer("sizes", torch.tensor(self.vocab_sizes, dtype=torch.int64),
                              persistent=False)
+        # host [F, 2] (lo, hi) arena-row range per feature, fixed for the
+        # life of the model: flat_ids() puts column f inside spans[f].  A
+        # plain attribute, not a buffer: it stays on the host.
+        self.spans = torch.stack(
+            [offsets, offsets + torch.tensor(self.vocab_sizes, dtype=torch.int64)],
+            dim=1).contiguous()
         if empty_init:
             arena = torch.empty(self.total_rows, self.cols)
         else:
@@ -246,7 +258,7 @@ class UnifiedMultiEmbedding(torch.nn.Module):
                              f"{self.num_features}")
         return _UnifiedGatherFn.apply(self.arena, self.flat_ids(ids), dense,
                                       self.num_features, self.dim,
-                                      self.defer_grads)
+                                      self.defer_grads, self.spans)
 
 
 def unified_col_scale(dim: int) -> torch.Tensor:

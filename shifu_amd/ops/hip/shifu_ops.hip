@@ -24,6 +24,9 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
+#include <algorithm>
+#include <map>
+#include <tuple>
 #include <vector>
 
 using bf16 = __hip_bfloat16;
@@ -3167,6 +3170,465 @@ void emb_update_unified(at::Tensor arena, at::Tensor acc, at::Tensor rows,
 }
 
 // ---------------------------------------------------------------------------
+// ONCE-HIT fused unified update (emb_update_unified_spans).
+//
+// On the deferred path entry e = b*F + f always lies in feature f's table
+// [lo_f, hi_f) and the tables are disjoint, so duplicates can only occur
+// inside one column of the [B, F] id matrix.  That makes duplicate
+// detection a per-column LDS bitmap job, and a row hit by exactly one entry
+// of the step has one writer: its accumulator add, denominator and weight
+// update are ONE plain read-modify-write of the row — no atomics, no second
+// pass over dgrad, no second random visit.  Three kernels:
+//   1. emb_local_ids_kernel + emb_dup_flag_kernel: flag[e] = 1 iff rows[e]
+//      is hit more than once (or lies outside its feature's table);
+//   2. emb_update_fused_kernel: flag 0 -> the whole update with plain loads
+//      and stores; flag 1 -> only the accsq work (one f32 atomicAdd);
+//   3. emb_scatter_dup_kernel: today's packed-bf16 atomic scatter, over
+//      the flagged entries only (duplicate tail).
+// Once-hit rows have one writer, duplicate rows receive only atomics, and
+// stores are byte-granular, so both kinds may share a 128-byte line.
+// ---------------------------------------------------------------------------
+#define EU_TB 64          // batch rows per id-transpose tile
+#define EU_MAX_F 128      // transpose tile: F * (EU_TB+1) ints of dynamic LDS
+#define EU_MAX_WG 2048    // cap on sum_f ceil(size_f / SPAN): every sub-range
+                          // workgroup scans its feature's whole column
+#define EU_MAX_PPL 4      // deep dword pairs per lane: D <= 256
+
+// rows per flag workgroup = 2^SHIFU_EMB_SPAN_LOG2 (16..18; two LDS bitmaps of
+// SPAN/8 bytes each)
+static int emb_span_log2() {
+  static int v = [] {
+    const char* e = getenv("SHIFU_EMB_SPAN_LOG2");
+    int x = e ? atoi(e) : 17;
+    return x < 16 ? 16 : (x > 18 ? 18 : x);
+  }();
+  return v;
+}
+
+long emb_dup_span() { return 1L << emb_span_log2(); }
+
+// rows [B, F] int64 -> feature-major local ids lidT [F, B] int32 (-1 = not
+// in the feature's table; such an entry is flagged 1 here and claimed by no
+// flag workgroup, so it takes the atomic path).  LDS-tiled so both the
+// reads and the writes are contiguous.
+__global__ void emb_local_ids_kernel(const long* __restrict__ rows,
+                                     const long* __restrict__ lohi,
+                                     int* __restrict__ lidT,
+                                     unsigned char* __restrict__ flags,
+                                     int B, int F) {
+  extern __shared__ int eu_tile[];               // [F][EU_TB + 1]
+  int b0 = blockIdx.x * EU_TB;
+  int nb = min(EU_TB, B - b0);
+  int cnt = nb * F;
+  long e0 = (long)b0 * F;
+  for (int i = threadIdx.x; i < cnt; i += blockDim.x) {
+    int bl = i / F, f = i - bl * F;
+    long lo = lohi[2 * f], hi = lohi[2 * f + 1];
+    long r = rows[e0 + i];
+    bool in = r >= lo && r < hi;
+    eu_tile[f * (EU_TB + 1) + bl] = in ? (int)(r - lo) : -1;
+    if (!in) flags[e0 + i] = 1;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < F * EU_TB; i += blockDim.x) {
+    int f = i / EU_TB, bl = i % EU_TB;
+    if (bl < nb) lidT[(long)f * B + b0 + bl] = eu_tile[f * (EU_TB + 1) + bl];
+  }
+}
+
+// one workgroup per (feature, sub-range of 2^LOG2 rows): wg[2*i] = feature,
+// wg[2*i+1] = sub-range index
+template <int LOG2>
+__global__ __launch_bounds__(1024) void emb_dup_flag_kernel(
+    const int* __restrict__ lidT, const int* __restrict__ wg,
+    unsigned char* __restrict__ flags, int B, int F) {
+  constexpr int WORDS = 1 << (LOG2 - 5);
+  __shared__ unsigned seen[WORDS];
+  __shared__ unsigned dup[WORDS];
+  const int f = wg[2 * blockIdx.x], sub = wg[2 * blockIdx.x + 1];
+  for (int i = threadIdx.x; i < WORDS; i += 1024) { seen[i] = 0u; dup[i] = 0u; }
+  __syncthreads();
+  const int* col = lidT + (long)f * B;
+  // every workgroup scans its feature's whole column: K loads in flight per
+  // thread, or the scan is one L2 latency per 1024 ids
+  constexpr int K = 8;
+  for (int b0 = threadIdx.x; b0 < B; b0 += 1024 * K) {
+    int lid[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      int b = b0 + k * 1024;
+      lid[k] = b < B ? col[b] : -1;
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      if (lid[k] >= 0 && (lid[k] >> LOG2) == sub) {
+        int l = lid[k] & ((1 << LOG2) - 1);
+        unsigned m = 1u << (l & 31);
+        if (atomicOr(&seen[l >> 5], m) & m) atomicOr(&dup[l >> 5], m);
+      }
+    }
+  }
+  __syncthreads();
+  for (int b0 = threadIdx.x; b0 < B; b0 += 1024 * K) {
+    int lid[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      int b = b0 + k * 1024;
+      lid[k] = b < B ? col[b] : -1;
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      if (lid[k] >= 0 && (lid[k] >> LOG2) == sub) {
+        int l = lid[k] & ((1 << LOG2) - 1);
+        flags[(long)(b0 + k * 1024) * F + f] =
+            (unsigned char)((dup[l >> 5] >> (l & 31)) & 1u);
+      }
+    }
+  }
+}
+
+DEVINL float eu_lo(unsigned u) { return __uint_as_float(u << 16); }
+DEVINL float eu_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
+DEVINL unsigned eu_bf16_bits(float x) {
+  bf16 h = __float2bfloat16(x);
+  return (unsigned)(*(const unsigned short*)&h);
+}
+// bf16(float(w) + float(bf16(sc * g))): the two roundings of the atomic
+// path, the addend first and then the sum
+DEVINL unsigned eu_upd(float w, float g, float sc) {
+  return eu_bf16_bits(w + eu_lo(eu_bf16_bits(sc * g)));
+}
+
+// 32 lanes per entry, one dword (a bf16 pair) per lane: lane k owns deep
+// pairs k, k+32, ...; lane 0 also the (wide, pad) dword and lane 1 the
+// accumulator.  Every group keeps U entries in flight: all their dgrad /
+// arena / accumulator loads are issued before the first use, and the row
+// ids and flags of the NEXT sweep are fetched behind them, so the ids ->
+// arena chain costs one random-load latency per sweep, not two.
+template <int PPL, int U>
+__global__ __launch_bounds__(256) void emb_update_fused_kernel(
+    unsigned* arena, float* acc,   // acc may point into the arena rows
+    const long* __restrict__ rows, const unsigned char* __restrict__ flags,
+    const bf16* __restrict__ dgrad, const bf16* __restrict__ wide,
+    unsigned n, unsigned F, int hp, long DP2,
+    long dstride, long dcol0, long wstride,
+    float scale, float eps, long astride, long aoff) {
+  const int lane = threadIdx.x & 31;
+  const unsigned gid = (blockIdx.x * blockDim.x + threadIdx.x) >> 5;
+  const unsigned sweep = ((gridDim.x * blockDim.x) >> 5) * U;
+  const float fDP = (float)(2 * DP2);
+  // base + 2 * sweep stays below 2^32: n < 2^31 - 2^24 (host check) and
+  // sweep <= 2^17
+  // Every load below is unconditional and straight-line, so the compiler
+  // can issue them back to back behind one counted wait: an entry past n
+  // loads entry n - 1 again, a lane past the deep pairs its row's last
+  // pair, a duplicate row its weights all the same, and lanes >= 2 the
+  // (wide, pad) dword of lane 0.  Only the stores are predicated.
+  long row[U];
+  unsigned fl[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    unsigned e = min(gid * U + u, n - 1);
+    row[u] = rows[e];
+    fl[u] = (unsigned)flags[e];
+  }
+  for (unsigned base = gid * U; base < n; base += sweep) {
+    unsigned g[U][PPL], w[U][PPL], tg[U], tw[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      unsigned e = min(base + u, n - 1);
+      unsigned b = e / F, f = e - b * F;
+      const unsigned* src =
+          (const unsigned*)(dgrad + (long)b * dstride + dcol0 + (long)f * (2 * hp));
+      const unsigned* dst = arena + row[u] * DP2;
+#pragma unroll
+      for (int j = 0; j < PPL; ++j) {
+        int dp = min(lane + 32 * j, hp - 1);
+        g[u][j] = src[dp];
+        w[u][j] = dst[dp];
+      }
+      tg[u] = (unsigned)*(const unsigned short*)(wide + (long)e * wstride);
+      const unsigned* ta = (lane == 1 && acc)
+          ? (const unsigned*)(acc + row[u] * astride + aoff) : dst + hp;
+      tw[u] = *ta;
+    }
+    long nrow[U];
+    unsigned nfl[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      unsigned e = min(base + sweep + u, n - 1);
+      nrow[u] = rows[e];
+      nfl[u] = (unsigned)flags[e];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const bool ok = base + u < n;
+      const bool plain = ok && fl[u] == 0u;
+      float sq = 0.0f;
+#pragma unroll
+      for (int j = 0; j < PPL; ++j) {
+        if (lane + 32 * j < hp) {
+          float a = eu_lo(g[u][j]), b = eu_hi(g[u][j]);
+          sq += a * a + b * b;
+        }
+      }
+      float wgf = eu_lo(tg[u]);
+      if (lane == 0) sq += wgf * wgf;
+#pragma unroll
+      for (int off = 16; off > 0; off >>= 1) sq += __shfl_xor(sq, off, 32);
+      const float addend = sq / fDP;
+      const float aold = __uint_as_float(__shfl(tw[u], 1, 32));
+      if (plain) {
+        float sc = scale;
+        if (acc) {
+          float anew = aold + addend;
+          sc = scale / (sqrtf(anew) + eps);
+          if (lane == 1) acc[row[u] * astride + aoff] = anew;
+        }
+        unsigned* dst = arena + row[u] * DP2;
+#pragma unroll
+        for (int j = 0; j < PPL; ++j) {
+          int dp = lane + 32 * j;
+          if (dp < hp) {
+            unsigned lo = eu_upd(eu_lo(w[u][j]), eu_lo(g[u][j]), sc);
+            unsigned hi = eu_upd(eu_hi(w[u][j]), eu_hi(g[u][j]), sc);
+            dst[dp] = lo | (hi << 16);
+          }
+        }
+        // wide column; the pad half of the dword keeps its (zero) bits
+        if (lane == 0)
+          dst[hp] = eu_upd(eu_lo(tw[u]), wgf, sc) | (tw[u] & 0xffff0000u);
+      } else if (ok && acc && lane == 1) {
+        // duplicate row: today's accsq work only
+        atomicAdd(&acc[row[u] * astride + aoff], addend);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      row[u] = nrow[u];
+      fl[u] = nfl[u];
+    }
+  }
+}
+
+// Duplicate tail: the atomic scatter of emb_scatter_uni_kernel for the
+// entries whose flag is set.  A wave reads the flags of 64 consecutive
+// entries in one load and walks only the set ones; every flagged lane has
+// fetched its own row id and accumulator before the walk, so the rows ->
+// acc chain of all of a wave's duplicates is in flight at once and an
+// unflagged entry costs nothing but its flag byte.  Runs after the fused
+// pass, so the accumulators of duplicate rows are complete.
+__global__ __launch_bounds__(256) void emb_scatter_dup_kernel(
+    bf16* __restrict__ arena, const long* __restrict__ rows,
+    const bf16* __restrict__ dgrad, const bf16* __restrict__ wide,
+    const float* __restrict__ acc, const unsigned char* __restrict__ flags,
+    unsigned n, unsigned F, long D, long DP, long dstride, long dcol0, long wstride,
+    float scale, float eps, long astride, long aoff) {
+  const int lane = threadIdx.x & 63;
+  const unsigned wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const unsigned step = ((gridDim.x * blockDim.x) >> 6) * 64;
+  const long hp = D >> 1;
+  for (unsigned base = wave * 64; base < n; base += step) {
+    unsigned e0 = base + lane;
+    bool hit = e0 < n && flags[e0] != 0;
+    long myrow = hit ? rows[e0] : 0;
+    float myav = (hit && acc) ? acc[myrow * astride + aoff] : 0.0f;
+    unsigned long long mask = __ballot(hit);
+    while (mask) {
+      int j = __ffsll((long long)mask) - 1;
+      mask &= mask - 1;
+      unsigned e = base + j;
+      long row = ((long)__shfl((int)(myrow >> 32), j) << 32)
+                 | (long)(unsigned)__shfl((int)myrow, j);
+      float av = __shfl(myav, j);
+      float sc = acc ? scale / (sqrtf(av) + eps) : scale;
+      unsigned b = e / F, f = e - b * F;
+      const bf16* src = dgrad + (long)b * dstride + dcol0 + (long)f * D;
+      bf16* dst = arena + row * DP;
+      // pair hp is (wide, pad): the pad column is fed a 0 addend
+      for (long dp = lane; dp <= hp; dp += 64) {
+        __hip_bfloat162 add;
+        if (dp < hp) {
+          add.x = __float2bfloat16(sc * __bfloat162float(src[dp * 2]));
+          add.y = __float2bfloat16(sc * __bfloat162float(src[dp * 2 + 1]));
+        } else {
+          add.x = __float2bfloat16(sc * __bfloat162float(wide[(long)e * wstride]));
+          add.y = __float2bfloat16(0.0f);
+        }
+        unsafeAtomicAdd((__hip_bfloat162*)(dst + dp * 2), add);
+      }
+    }
+  }
+}
+
+// device tables derived from a host [F, 2] span table, built once per
+// (device, SPAN, table contents) and kept for the life of the process
+struct EuTables {
+  at::Tensor lohi;   // [F, 2] int64 on the device
+  at::Tensor wg;     // [W, 2] int32 (feature, sub-range) on the device
+  long W;
+};
+
+static const EuTables& eu_tables(const at::Tensor& spans, long F, const at::Device& dev) {
+  TORCH_CHECK(!spans.is_cuda() && spans.scalar_type() == at::kLong && spans.is_contiguous()
+              && spans.dim() == 2 && spans.size(0) == F && spans.size(1) == 2,
+              "spans must be a contiguous host [F, 2] int64 table");
+  static std::map<std::tuple<int, int, std::vector<long>>, EuTables> cache;
+  const int lg = emb_span_log2();
+  const long* sp = spans.data_ptr<long>();
+  auto key = std::make_tuple((int)dev.index(), lg, std::vector<long>(sp, sp + 2 * F));
+  auto it = cache.find(key);
+  if (it != cache.end()) return it->second;
+  std::vector<std::pair<long, long>> sorted;
+  std::vector<int> wgv;
+  for (long f = 0; f < F; ++f) {
+    long lo = sp[2 * f], hi = sp[2 * f + 1];
+    TORCH_CHECK(lo >= 0 && hi >= lo && hi - lo < (1L << 31), "bad span for feature ", f);
+    sorted.emplace_back(lo, hi);
+    long subs = (hi - lo + (1L << lg) - 1) >> lg;
+    // past the cap the caller falls back; do not build a huge table
+    for (long s = 0; s < subs && (long)wgv.size() <= 2 * EU_MAX_WG; ++s) {
+      wgv.push_back((int)f);
+      wgv.push_back((int)s);
+    }
+  }
+  std::sort(sorted.begin(), sorted.end());
+  for (size_t i = 1; i < sorted.size(); ++i)
+    TORCH_CHECK(sorted[i - 1].second <= sorted[i].first, "feature spans overlap");
+  EuTables t;
+  t.W = (long)wgv.size() / 2;
+  t.lohi = spans.to(dev);
+  auto wg_host = at::empty({std::max(t.W, 1L), 2}, at::TensorOptions().dtype(at::kInt));
+  std::copy(wgv.begin(), wgv.end(), wg_host.data_ptr<int>());
+  t.wg = wg_host.to(dev);
+  return cache.emplace(std::move(key), std::move(t)).first->second;
+}
+
+static bool eu_shape_ok(const at::Tensor& rows, long F) {
+  long n = rows.numel();
+  return F > 0 && F <= EU_MAX_F && n % F == 0 && n < (1L << 31) - (1L << 24);
+}
+
+// flag[e] = 1 iff rows[e] is hit more than once (or is outside its span)
+static at::Tensor eu_flags(const at::Tensor& rows, long F, const EuTables& t) {
+  long n = rows.numel();
+  int B = (int)(n / F);
+  auto s = cur_stream();
+  auto flags = at::empty({n}, rows.options().dtype(at::kByte));
+  auto lidT = at::empty({n}, rows.options().dtype(at::kInt));
+  hipLaunchKernelGGL(emb_local_ids_kernel, dim3((unsigned)((B + EU_TB - 1) / EU_TB)),
+                     dim3(256), (size_t)F * (EU_TB + 1) * sizeof(int), s,
+                     (const long*)rows.data_ptr(), (const long*)t.lohi.data_ptr(),
+                     (int*)lidT.data_ptr(), (unsigned char*)flags.data_ptr(), B, (int)F);
+  if (t.W > 0) {
+    dim3 grid((unsigned)t.W), block(1024);
+    const int* lp = (const int*)lidT.data_ptr();
+    const int* wp = (const int*)t.wg.data_ptr();
+    unsigned char* fp = (unsigned char*)flags.data_ptr();
+    switch (emb_span_log2()) {
+      case 16: hipLaunchKernelGGL(emb_dup_flag_kernel<16>, grid, block, 0, s, lp, wp, fp, B, (int)F); break;
+      case 17: hipLaunchKernelGGL(emb_dup_flag_kernel<17>, grid, block, 0, s, lp, wp, fp, B, (int)F); break;
+      default: hipLaunchKernelGGL(emb_dup_flag_kernel<18>, grid, block, 0, s, lp, wp, fp, B, (int)F); break;
+    }
+  }
+  return flags;
+}
+
+at::Tensor emb_dup_flags(at::Tensor rows, long F, at::Tensor spans) {
+  CHECK_GPU(rows); CHECK_CONTIG(rows);
+  TORCH_CHECK(rows.scalar_type() == at::kLong, "rows must be int64");
+  TORCH_CHECK(eu_shape_ok(rows, F), "emb_dup_flags: rows must be [B*F], F <= ", EU_MAX_F);
+  const EuTables& t = eu_tables(spans, F, rows.device());
+  TORCH_CHECK(t.W <= EU_MAX_WG, "emb_dup_flags: more than ", EU_MAX_WG, " sub-ranges");
+  if (!rows.numel()) return at::empty({0}, rows.options().dtype(at::kByte));
+  return eu_flags(rows, F, t);
+}
+
+template <int PPL>
+static void eu_launch_fused(hipStream_t s, unsigned blocks, unsigned* arena, float* accw,
+                            const long* rows, const unsigned char* flags, const bf16* dgrad,
+                            const bf16* wide, unsigned n, unsigned F, int hp, long DP2,
+                            long dstride, long dcol0, long wstride, float scale, float eps,
+                            long astride, long aoff) {
+  hipLaunchKernelGGL((emb_update_fused_kernel<PPL, 4>), dim3(blocks), dim3(256), 0, s,
+                     arena, accw, rows, flags, dgrad, wide, n, F, hp, DP2,
+                     dstride, dcol0, wstride, scale, eps, astride, aoff);
+}
+
+// emb_update_unified for the deferred layout (entry e = b*F + f inside
+// spans[f]): duplicate flags, fused plain pass, atomic tail for duplicates.
+// Shapes it does not cover (and SHIFU_EMB_BINNED=1) take emb_update_unified.
+void emb_update_unified_spans(at::Tensor arena, at::Tensor acc, at::Tensor rows,
+                              at::Tensor dgrad, long dcol0, at::Tensor wide,
+                              long wstride, long F, double lr, double eps,
+                              bool adagrad, bool acc_in_arena, at::Tensor spans) {
+  long n = rows.numel();
+  if (!n) return;
+  long DP = arena.size(1);
+  long D = DP - (acc_in_arena ? 4 : 2);
+  CHECK_GPU(rows); CHECK_CONTIG(rows);
+  TORCH_CHECK(rows.scalar_type() == at::kLong, "rows must be int64");
+  bool ok = !emb_binned_mode() && eu_shape_ok(rows, F) && D > 0 && D % 2 == 0
+            && D / 2 <= 32 * EU_MAX_PPL;
+  const EuTables* t = nullptr;
+  if (ok) {
+    t = &eu_tables(spans, F, rows.device());
+    ok = t->W <= EU_MAX_WG;
+  }
+  if (!ok) {
+    emb_update_unified(arena, acc, rows, dgrad, dcol0, wide, wstride, F, lr, eps,
+                       adagrad, acc_in_arena);
+    return;
+  }
+  CHECK_GPU(arena); CHECK_CONTIG(arena); CHECK_BF16(arena);
+  CHECK_GPU(dgrad); CHECK_BF16(dgrad);
+  CHECK_GPU(wide); CHECK_BF16(wide);
+  long dstride = dgrad.size(1);
+  TORCH_CHECK(dgrad.stride(1) == 1 && dgrad.stride(0) == dstride,
+              "dgrad must be row-contiguous");
+  TORCH_CHECK(dcol0 % 2 == 0 && dstride % 2 == 0 && DP % 2 == 0,
+              "unified update needs 4B-aligned deep columns");
+  TORCH_CHECK(dgrad.size(0) * F == n && dcol0 + F * D <= dstride,
+              "dgrad must be [n / F, >= dcol0 + F*D]");
+  TORCH_CHECK(wide.numel() == n, "wide must hold one gradient per entry");
+  auto s = cur_stream();
+  float* accw = nullptr;
+  long astride = 1, aoff = 0;
+  if (acc_in_arena) {
+    accw = adagrad ? (float*)arena.data_ptr() : nullptr;
+    astride = DP / 2;
+    aoff = (D + 2) / 2;
+  } else if (adagrad) {
+    CHECK_F32(acc);
+    TORCH_CHECK(acc.numel() >= arena.size(0), "accumulator must be [R]");
+    accw = (float*)acc.data_ptr();
+  }
+  at::Tensor flags = eu_flags(rows, F, *t);
+  const unsigned char* fp = (const unsigned char*)flags.data_ptr();
+  int hp = (int)(D / 2);
+  int ppl = (hp + 31) / 32;
+  // 8 groups x 4 entries per block.  Measured at the bench shape (72 VGPRs,
+  // 7 waves per SIMD): 3584 blocks = two full rounds of resident waves beat
+  // 1792, 2048 and U = 2 or 8 (profiles/emb_unique_update.md)
+  unsigned blocks = (unsigned)std::min((n + 31) / 32, (long)3584);
+  unsigned* a32 = (unsigned*)arena.data_ptr();
+  const long* rp = (const long*)rows.data_ptr();
+  const bf16* dg = (const bf16*)dgrad.data_ptr();
+  const bf16* wd = (const bf16*)wide.data_ptr();
+#define EU_FUSED(P) eu_launch_fused<P>(s, blocks, a32, accw, rp, fp, dg, wd, (unsigned)n, \
+                                       (unsigned)F, hp, DP / 2, dstride, dcol0, wstride,  \
+                                       (float)-lr, (float)eps, astride, aoff)
+  if (ppl <= 1) EU_FUSED(1);
+  else if (ppl == 2) EU_FUSED(2);
+  else EU_FUSED(4);
+#undef EU_FUSED
+  hipLaunchKernelGGL(emb_scatter_dup_kernel, dim3(scat_blocks(n)), dim3(256), 0, s,
+                     (bf16*)arena.data_ptr(), rp, dg, wd, (const float*)accw, fp,
+                     (unsigned)n, (unsigned)F, D, DP, dstride, dcol0, wstride, (float)-lr,
+                     (float)eps, astride, aoff);
+}
+
+// ---------------------------------------------------------------------------
 // BINNED unified update — atomic-free owner-partitioned rewrite of
 // accsq+scatter.  The atomic chain issues ~33 packed-bf16 atomics per entry
 // (~28M per bench step), which bounds it on atomic issue/L2-RMW, not HBM.
@@ -3728,6 +4190,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("emb_gather_split", &emb_gather_split);
   m.def("emb_update_unified", &emb_update_unified);
   m.def("emb_update_unified_binned", &emb_update_unified_binned);
+  m.def("emb_update_unified_spans", &emb_update_unified_spans);
+  m.def("emb_dup_flags", &emb_dup_flags);
+  m.def("emb_dup_span", &emb_dup_span);
   m.def("emb_sgd_step", &emb_sgd_step);
   m.def("emb_adagrad_step", &emb_adagrad_step);
   m.def("mlp_score_fused", &mlp_score_fused, py::arg("x"), py::arg("packed_weights"),

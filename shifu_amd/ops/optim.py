@@ -15,6 +15,7 @@ accumulator per row).
 from __future__ import annotations
 
 import math
+import os
 from typing import Dict, List, Optional
 
 import torch
@@ -122,10 +123,19 @@ class FusedOptimizer:
             ext = hip_ops()
             acc = (self.emb_state[idx] if (adagrad and not in_arena)
                    else torch.empty(0, device=p.device, dtype=torch.float32))
-            for (rows, dout, nd, dwide, F, _D) in stash:
-                ext.emb_update_unified(p.data, acc, rows, dout, nd,
-                                       dwide, 1, F, self.emb_lr, self.eps,
-                                       adagrad, in_arena)
+            # SHIFU_EMB_UNIQUE=0 restores the all-atomic accsq + scatter chain
+            unique = os.environ.get("SHIFU_EMB_UNIQUE", "1") != "0"
+            for (rows, dout, nd, dwide, F, _D, spans) in stash:
+                if unique and spans is not None:
+                    # once-hit rows: one plain fused read-modify-write;
+                    # duplicates keep the atomic chain
+                    ext.emb_update_unified_spans(
+                        p.data, acc, rows, dout, nd, dwide, 1, F, self.emb_lr,
+                        self.eps, adagrad, in_arena, spans)
+                else:
+                    ext.emb_update_unified(p.data, acc, rows, dout, nd,
+                                           dwide, 1, F, self.emb_lr, self.eps,
+                                           adagrad, in_arena)
             p._unified_grads = []
             return
         if p.grad is None:
