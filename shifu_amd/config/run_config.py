@@ -105,6 +105,10 @@ class RunConfig:
     graphs: str = "auto"                 # hipGraph-captured steps: "auto"|"on"|"off"
                                          # (auto = on for single-GPU cuda, full
                                          # batches, no window mode)
+    fused_mlp_step: bool = False         # eligible ShifuMLP at world 1: forward,
+                                         # loss and backward run as ONE kernel
+                                         # (ops/fused_mlp.py); an ineligible
+                                         # model is an error, never a fallback
 
     def resolved_backend(self) -> str:
         if self.backend != "auto":

@@ -48,6 +48,13 @@ class ShifuMLP(torch.nn.Module):
             x = layer(x)
         return self.shifu_output_0(x).reshape(-1)  # logits [B]
 
+    def fused_loss(self, dense: torch.Tensor, target: torch.Tensor,
+                   weight: torch.Tensor, kind: str = "weighted_mse") -> torch.Tensor:
+        """Forward + weighted loss + backward in one kernel (ops/fused_mlp.py):
+        a scalar whose backward() delivers the gradients the kernel computed."""
+        from shifu_amd.ops.fused_mlp import fused_loss
+        return fused_loss(self, dense, target, weight, kind)
+
     @torch.no_grad()
     def predict(self, dense: torch.Tensor, cats: Optional[torch.Tensor] = None) -> torch.Tensor:
         return predict_proba(self.forward(dense, cats))

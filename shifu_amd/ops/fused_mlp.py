@@ -358,3 +358,169 @@ def attach_fused_ensemble(model) -> PackedEnsemble:
     model.predict_members = lambda dense, cats=None: fused_ensemble_predict(
         packed, dense, return_members=True)[1]
     return packed
+
+
+# ---------------------------------------------------------------------------
+# Training: forward + loss + backward in one kernel (ops/hip/fused_mlp_grad.hip).
+#
+# `mlp_loss_grad_fused` keeps two fragment-ordered images of the weights (W for
+# the forward pass, W^T for dgrad) in LDS, built on the device from the live
+# fp32 parameters every call, and streams 64-row block tiles through forward,
+# loss, dgrad and a block-level wgrad whose accumulators stay in registers.
+# Per-block partial gradients are summed in block order by a second small
+# kernel that also applies the SUM_BY_NONZERO_WEIGHTS division, so the result
+# is deterministic and nothing is read back to the host.
+#
+# Rounding points: the forward pass is `mlp_score_fused`'s; dlogit and every
+# dZ_l = dH_l * act'(H_l) are rounded to bf16 before they feed dgrad, wgrad and
+# the bias column sum; act' is taken from the bf16 layer output; dH, dW and db
+# accumulate in fp32.
+
+GRAD_WAVES = 4                # waves per block, 16 rows each
+GRAD_ROWS = 16 * GRAD_WAVES   # rows per block pass
+GRAD_LDS_LIMIT = 160 * 1024   # all of a gfx950 CU's LDS: one block per CU
+GRAD_MAX_INPUT = 512          # layer-0 fragments live in registers (16 k-steps)
+GRAD_MAX_SLOTS = 40           # dW/db accumulator tiles one wave can own
+_GRAD_TAIL = 64               # loss/count reduction scratch
+
+
+def _grad_lds_bytes(shapes: List[Tuple[int, int]]) -> int:
+    """LDS of one training block for layers [(N, K), ...] — the launcher in
+    fused_mlp_grad.hip derives the same map and checks it again."""
+    image = _blob_bytes(shapes) + sum(_ceil_to(k, 16) * _ceil_to(n, 32) * 2
+                                      for n, k in shapes[1:])
+    # per wave: every hidden layer's output (16 rows x Npad32 bf16) and two
+    # ping-pong dZ buffers at the widest Npad32 of the layers that need dgrad
+    hidden = sum(32 * _ceil_to(n, 32) for n, _ in shapes[:-1])
+    dz = 32 * max([32] + [_ceil_to(n, 32) for n, _ in shapes[1:]])
+    # block staging, m-contiguous: each layer's input and its dZ, 64 rows
+    stage = sum((_ceil_to(k, 16) + _ceil_to(n, 16)) * GRAD_ROWS * 2
+                for n, k in shapes)
+    return image + GRAD_WAVES * (hidden + 2 * dz) + stage + _GRAD_TAIL
+
+
+def _grad_slots(shapes: List[Tuple[int, int]]) -> int:
+    """dW tiles plus one db tile per 16 output features, dealt over the waves."""
+    tiles = sum(_ceil_to(n, 16) // 16 * (_ceil_to(k, 16) // 16 + 1)
+                for n, k in shapes)
+    return (tiles + GRAD_WAVES - 1) // GRAD_WAVES
+
+
+def fused_grad_eligible(model) -> Tuple[bool, str]:
+    """(True, "") when `model` can train through the fused loss+grad kernel,
+    else (False, reason)."""
+    ok, why = fused_eligible(model)
+    if not ok:
+        return ok, why
+    shapes = _shapes_of(model)
+    if shapes[0][1] > GRAD_MAX_INPUT:
+        return False, (f"input width {shapes[0][1]} > {GRAD_MAX_INPUT} (the "
+                       f"layer-0 fragments stay in registers)")
+    lds = _grad_lds_bytes(shapes)
+    if lds > GRAD_LDS_LIMIT:
+        return False, (f"weight images + row staging + activation buffers "
+                       f"need {lds} B of LDS > {GRAD_LDS_LIMIT}")
+    slots = _grad_slots(shapes)
+    if slots > GRAD_MAX_SLOTS:
+        return False, (f"{slots} gradient tiles per wave > {GRAD_MAX_SLOTS} "
+                       f"register-resident accumulators")
+    return True, ""
+
+
+def _bf16_round(t: torch.Tensor) -> torch.Tensor:
+    return t.to(torch.bfloat16).float()
+
+
+def _emulate_loss_and_grad(layers, dense, target, weight, kind: int):
+    """Pure-torch loss and gradients with exactly the kernel's rounding
+    points.  layers: [(W fp32 [N, K], b fp32 [N], act id), ...]."""
+    from shifu_amd.ops.linear import _act_grad_from_y_ref
+    x = _bf16_round(dense.detach().float().cpu())
+    y = target.detach().float().cpu()
+    w = weight.detach().float().cpu()
+    ws = [_bf16_round(W.detach().float().cpu()) for W, _, _ in layers]
+    xs = [x]
+    for i, (_, b, act) in enumerate(layers[:-1]):
+        z = xs[-1] @ ws[i].t() + b.detach().float().cpu()
+        xs.append(_bf16_round(_act_fwd_ref(z, act)))
+    z = (xs[-1] @ ws[-1].t() + layers[-1][1].detach().float().cpu()).reshape(-1)
+    p = torch.sigmoid(z)
+    if kind == 0:
+        per = w * (p - y) ** 2
+        dl = w * 2.0 * (p - y) * p * (1.0 - p)
+    else:
+        per = w * torch.nn.functional.binary_cross_entropy_with_logits(
+            z, y, reduction="none")
+        dl = w * (p - y)
+    cnt = (w != 0).float().sum().clamp_min(1e-12)
+    dz = _bf16_round(dl).reshape(-1, 1)
+    grads = [None] * len(layers)
+    for i in range(len(layers) - 1, -1, -1):
+        grads[i] = ((dz.t() @ xs[i]) / cnt, dz.sum(dim=0) / cnt)
+        if i > 0:
+            dz = _bf16_round(_act_grad_from_y_ref(dz @ ws[i], xs[i], layers[i - 1][2]))
+    return per.sum() / cnt, grads
+
+
+def fused_loss_and_grad(model, dense: torch.Tensor, target: torch.Tensor,
+                        weight: torch.Tensor, kind: str = "weighted_mse",
+                        max_blocks: int = 0):
+    """(loss, [(dW [N, K], db [N]), ...]) for one batch: the normalised
+    weighted loss of ops/loss.py as a 0-d fp32 tensor and its fp32 gradient
+    with respect to every layer's weight and bias, in layer order."""
+    from shifu_amd.ops.loss import _KIND_IDS
+    ok, why = fused_grad_eligible(model)
+    if not ok:
+        raise ValueError(f"model is not eligible for the fused training step: {why}")
+    kind_id = _KIND_IDS[kind.lower()]
+    layers = _layers_of(model)
+    if dense.dim() != 2 or dense.shape[1] != layers[0].in_features:
+        raise ValueError(f"expected dense [B, {layers[0].in_features}], got "
+                         f"{tuple(dense.shape)}")
+    ext = require_hip() if dense.is_cuda else None
+    if ext is None:            # CPU rows, or the explicit eager A/B opt-in
+        loss, grads = _emulate_loss_and_grad(
+            [(l.weight, l.bias, l._act) for l in layers], dense, target, weight,
+            kind_id)
+        dev = dense.device
+        return loss.to(dev), [(dw.to(dev), db.to(dev)) for dw, db in grads]
+    x = dense.detach()
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        x = x.float()
+    loss, flat = ext.mlp_loss_grad_fused(
+        x.contiguous(), target.detach().float().contiguous(),
+        weight.detach().float().contiguous(),
+        [l.weight.detach().contiguous() for l in layers],
+        [l.bias.detach().contiguous() for l in layers],
+        [l._act for l in layers], kind_id, max_blocks)
+    grads, off = [], 0
+    for l in layers:
+        n, k = l.out_features, l.in_features
+        grads.append((flat[off:off + n * k].view(n, k),
+                      flat[off + n * k:off + n * k + n]))
+        off += n * k + n
+    return loss, grads
+
+
+class _FusedLossFn(torch.autograd.Function):
+    """The kernel runs once, in forward; backward hands out its gradients
+    scaled by grad_out, so they reach .grad through AccumulateGrad like any
+    other gradient (window mode and tail batches need nothing special)."""
+
+    @staticmethod
+    def forward(ctx, model, dense, target, weight, kind, *params):
+        loss, grads = fused_loss_and_grad(model, dense, target, weight, kind)
+        ctx.save_for_backward(*[g for pair in grads for g in pair])
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return (None, None, None, None, None,
+                *[g * grad_out for g in ctx.saved_tensors])
+
+
+def fused_loss(model, dense: torch.Tensor, target: torch.Tensor,
+               weight: torch.Tensor, kind: str = "weighted_mse") -> torch.Tensor:
+    """Scalar loss, autograd-connected to the model's parameters."""
+    params = [p for l in _layers_of(model) for p in (l.weight, l.bias)]
+    return _FusedLossFn.apply(model, dense, target, weight, kind, *params)

@@ -37,21 +37,13 @@
 #include <cstdint>
 #include <vector>
 
+#include "fused_mlp_common.h"
+
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-#define FMLP_DEVINL __device__ __forceinline__
-
-constexpr int FMLP_MAX_LAYERS = 8;
 constexpr int FMLP_MAX_WAVES = 8;           // 512 threads
 constexpr int FMLP_LDS_LIMIT = 131072;      // same ceiling as V4_LDS_BYTES
 constexpr int FMLP_MAX_KS0 = 32;            // layer-0 fragments live in VGPRs
-
-// activation ids shared with shifu_amd/ops/linear.py and shifu_ops.hip
-enum { FACT_NONE = 0, FACT_SIGMOID = 1, FACT_TANH = 2, FACT_RELU = 3, FACT_LEAKY = 4 };
-constexpr float FMLP_LEAKY_SLOPE = 0.01f;
 
 struct MlpLayer {
   int w_off;   // byte offset of the fragment-ordered bf16 [Npad, Kpad] image
@@ -67,35 +59,6 @@ struct MlpTable {
   int act_bytes;     // bytes of ONE per-wave activation buffer (two per wave)
   MlpLayer l[FMLP_MAX_LAYERS];
 };
-
-FMLP_DEVINL float fmlp_act(float z, int act) {
-  switch (act) {
-    case FACT_SIGMOID: return 1.0f / (1.0f + __expf(-z));
-    case FACT_TANH:    return tanhf(z);
-    case FACT_RELU:    return z > 0.0f ? z : 0.0f;
-    case FACT_LEAKY:   return z > 0.0f ? z : FMLP_LEAKY_SLOPE * z;
-    default:           return z;
-  }
-}
-
-// fp32 -> bf16 bits, round-to-nearest-even (NaN stays a quiet NaN)
-FMLP_DEVINL unsigned fmlp_bf16_bits(float f) {
-  unsigned u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-
-FMLP_DEVINL unsigned fmlp_pack2(float lo, float hi) {
-  return fmlp_bf16_bits(lo) | (fmlp_bf16_bits(hi) << 16);
-}
-
-// LDS traffic between layers is wave-private and the LDS serves one wave's
-// instructions in issue order; this only stops the compiler from moving a
-// fragment read above the stores (from other lanes) that produce it.
-FMLP_DEVINL void fmlp_wave_lds_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
 
 // Epilogue of one 16-feature tile: + bias, activation, then either the fp32
 // score store (head) or the bf16 hand-off to the next layer's B fragments.
@@ -409,8 +372,6 @@ void mlp_score_fused_ensemble_kernel(const float* __restrict__ x,
     fmlp_wave_lds_fence();
   }
 }
-
-inline int ceil_to(int v, int a) { return (v + a - 1) / a * a; }
 
 template <int KS0, bool VEC>
 void launch(int blocks, int threads, int lds, hipStream_t s, const float* x,

@@ -4150,6 +4150,11 @@ at::Tensor mlp_score_fused(at::Tensor x, at::Tensor packed,
 std::vector<at::Tensor> mlp_score_fused_ensemble(
     at::Tensor x, std::vector<at::Tensor> blobs, std::vector<at::Tensor> tables,
     bool return_members, int64_t max_blocks, int64_t waves);
+// fused forward+loss+backward of an LDS-resident MLP — defined in fused_mlp_grad.hip
+std::vector<at::Tensor> mlp_loss_grad_fused(
+    at::Tensor x, at::Tensor target, at::Tensor weight,
+    std::vector<at::Tensor> weights, std::vector<at::Tensor> biases,
+    std::vector<int64_t> acts, int64_t kind, int64_t max_blocks);
 
 // ---------------------------------------------------------------------------
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -4200,4 +4205,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mlp_score_fused_ensemble", &mlp_score_fused_ensemble, py::arg("x"),
         py::arg("blobs"), py::arg("tables"), py::arg("return_members") = false,
         py::arg("max_blocks") = 0, py::arg("waves") = 8);
+  m.def("mlp_loss_grad_fused", &mlp_loss_grad_fused, py::arg("x"), py::arg("target"),
+        py::arg("weight"), py::arg("weights"), py::arg("biases"), py::arg("acts"),
+        py::arg("kind") = 0, py::arg("max_blocks") = 0);
 }

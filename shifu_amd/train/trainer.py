@@ -285,6 +285,16 @@ class Trainer:
                            and not isinstance(self.train_data, StreamingData))
         self._graph = None
         self._gb: Optional[DeviceData] = None
+        # one-kernel forward+loss+backward for LDS-resident MLPs
+        self._fused_step = bool(getattr(rc, "fused_mlp_step", False))
+        if self._fused_step:
+            from shifu_amd.ops.fused_mlp import fused_grad_eligible
+            ok, why = fused_grad_eligible(self.model)
+            if ok and world_size != 1:
+                ok, why = False, f"world size {world_size} != 1"
+            if not ok:
+                raise ValueError(f"fused_mlp_step is set but the model cannot "
+                                 f"use the fused training step: {why}")
 
     # ------------------------------------------------------------------ steps
     def train_step(self, batch: DeviceData, sync: bool = True) -> torch.Tensor:
@@ -293,10 +303,15 @@ class Trainer:
         host readback would stall the pipeline)."""
         tr = self.tracer
         self.aggregator.set_sync(sync)
-        with tr.phase("fwd"):
-            logits = self.model(batch.dense, batch.cats)
-        with tr.phase("loss"):
-            loss = weighted_loss(logits, batch.target, batch.weight, self.loss_kind)
+        if self._fused_step:
+            with tr.phase("fwd"):
+                loss = self.model.fused_loss(batch.dense, batch.target,
+                                             batch.weight, self.loss_kind)
+        else:
+            with tr.phase("fwd"):
+                logits = self.model(batch.dense, batch.cats)
+            with tr.phase("loss"):
+                loss = weighted_loss(logits, batch.target, batch.weight, self.loss_kind)
         with tr.phase("bwd"):
             loss.backward()
         if sync:
@@ -324,8 +339,12 @@ class Trainer:
         gb = self._gb
 
         def body():
-            logits = self.model(gb.dense, gb.cats)
-            loss = weighted_loss(logits, gb.target, gb.weight, self.loss_kind)
+            if self._fused_step:
+                loss = self.model.fused_loss(gb.dense, gb.target, gb.weight,
+                                             self.loss_kind)
+            else:
+                logits = self.model(gb.dense, gb.cats)
+                loss = weighted_loss(logits, gb.target, gb.weight, self.loss_kind)
             loss.backward()
             self.aggregator.finish()
             self.optimizer.step()
