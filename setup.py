@@ -21,7 +21,8 @@ setup(
             name="shifu_amd.ops._shifu_hip",
             sources=["shifu_amd/ops/hip/shifu_ops.hip",
                      "shifu_amd/ops/hip/fused_mlp.hip",
-                     "shifu_amd/ops/hip/fused_mlp_grad.hip"],
+                     "shifu_amd/ops/hip/fused_mlp_grad.hip",
+                     "shifu_amd/ops/hip/eval_hist.hip"],
             extra_compile_args={
                 "cxx": ["-O3", "-std=c++17"],
                 "nvcc": ["-O3", "-std=c++17", "--offload-arch=gfx950"],

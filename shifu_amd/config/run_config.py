@@ -109,6 +109,12 @@ class RunConfig:
                                          # loss and backward run as ONE kernel
                                          # (ops/fused_mlp.py); an ineligible
                                          # model is an error, never a fallback
+    device_eval: bool = False            # world 1: Trainer.evaluate keeps loss
+                                         # and score histograms on the device
+                                         # and reports the BINNED AUC plus KS
+                                         # (ops/eval_hist.py); off = host
+                                         # rank AUC over every score
+    device_eval_bins: int = 1024         # score bins, a power of two in [32, 4096]
 
     def resolved_backend(self) -> str:
         if self.backend != "auto":

@@ -45,56 +45,6 @@ constexpr int FMLP_MAX_WAVES = 8;           // 512 threads
 constexpr int FMLP_LDS_LIMIT = 131072;      // same ceiling as V4_LDS_BYTES
 constexpr int FMLP_MAX_KS0 = 32;            // layer-0 fragments live in VGPRs
 
-struct MlpLayer {
-  int w_off;   // byte offset of the fragment-ordered bf16 [Npad, Kpad] image
-  int b_off;   // byte offset of the fp32 bias[Npad]
-  int nt;      // Npad / 16
-  int ks;      // Kpad / 32
-  int act;
-};
-
-struct MlpTable {
-  int n_layers;
-  int blob_bytes;    // multiple of 16
-  int act_bytes;     // bytes of ONE per-wave activation buffer (two per wave)
-  MlpLayer l[FMLP_MAX_LAYERS];
-};
-
-// Epilogue of one 16-feature tile: + bias, activation, then either the fp32
-// score store (head) or the bf16 hand-off to the next layer's B fragments.
-FMLP_DEVINL void fmlp_epilogue(f32x4 acc, const MlpLayer& L, int nt, bool last,
-                               const unsigned char* smem, unsigned char* dst,
-                               float* __restrict__ out, long row, long B,
-                               int m, int kg) {
-  const int n0 = nt * 16 + kg * 4;            // first of this lane's 4 features
-  const float4 bias = *(const float4*)(smem + L.b_off + n0 * 4);
-  if (last) {
-    // head: feature 0 of every row sits in r=0 of lanes 0..15; logit stays fp32
-    if (kg == 0 && row < B)
-      out[row] = 1.0f / (1.0f + __expf(-(acc[0] + bias.x)));
-    return;
-  }
-  const float v0 = fmlp_act(acc[0] + bias.x, L.act);
-  const float v1 = fmlp_act(acc[1] + bias.y, L.act);
-  const float v2 = fmlp_act(acc[2] + bias.z, L.act);
-  const float v3 = fmlp_act(acc[3] + bias.w, L.act);
-  uint2 p;
-  p.x = fmlp_pack2(v0, v1);
-  p.y = fmlp_pack2(v2, v3);
-  // feature n is reduction index k of the next layer: fragment slot
-  // (k/32, lane' = (k%32/8)*16 + m), element k%8 (0 or 4 here)
-  const int off = (((n0 >> 5) * 64 + ((n0 & 31) >> 3) * 16 + m) << 4) + ((n0 & 7) << 1);
-  *(uint2*)(dst + off) = p;
-}
-
-// Zero the 16-feature tile `nt` of the next layer's input (Kpad = ceil32(N)
-// can exceed Npad = ceil16(N); stale LDS there could hold NaN bit patterns).
-FMLP_DEVINL void fmlp_zero_tile(unsigned char* dst, int nt, int m, int kg) {
-  const int n0 = nt * 16 + kg * 4;
-  const int off = (((n0 >> 5) * 64 + ((n0 & 31) >> 3) * 16 + m) << 4) + ((n0 & 7) << 1);
-  *(uint2*)(dst + off) = make_uint2(0u, 0u);
-}
-
 // KS0: compile-time bound on the layer-0 k-steps (its fragments stay in VGPRs)
 // VEC : rows are 16-byte aligned (K0 % 4 == 0 and aligned base) -> float4 loads
 template <int KS0, bool VEC>
@@ -443,15 +393,8 @@ at::Tensor mlp_score_fused(at::Tensor x, at::Tensor packed,
               "x must be contiguous fp32 [B, K0]");
   TORCH_CHECK(packed.scalar_type() == at::kByte && packed.dim() == 1 &&
               packed.is_contiguous(), "packed must be a contiguous uint8 blob");
-  TORCH_CHECK(!layer_table.is_cuda() && layer_table.scalar_type() == at::kInt &&
-              layer_table.dim() == 2 && layer_table.size(1) == 4 &&
-              layer_table.is_contiguous(),
-              "layer_table must be a CPU int32 [L, 4] tensor");
   TORCH_CHECK(waves == 2 || waves == 4 || waves == 8, "waves must be 2, 4 or 8");
   TORCH_CHECK(max_blocks >= 0, "max_blocks must be >= 0");
-  const long L = layer_table.size(0);
-  TORCH_CHECK(L >= 1 && L <= FMLP_MAX_LAYERS, "fused MLP supports 1..",
-              FMLP_MAX_LAYERS, " layers, got ", L);
   const long B = x.size(0);
   const int K0 = (int)x.size(1);
   const long blob_bytes = packed.numel();
@@ -460,32 +403,7 @@ at::Tensor mlp_score_fused(at::Tensor x, at::Tensor packed,
   TORCH_CHECK((reinterpret_cast<uintptr_t>(packed.data_ptr()) & 15) == 0,
               "packed blob must be 16-byte aligned");
 
-  const int* tab = layer_table.data_ptr<int>();
-  MlpTable t{};
-  t.n_layers = (int)L;
-  t.blob_bytes = (int)blob_bytes;
-  int prev = K0, max_kpad = 32;
-  long expect_off = 0;
-  for (long i = 0; i < L; ++i) {
-    const int off = tab[i * 4 + 0], N = tab[i * 4 + 1], K = tab[i * 4 + 2],
-              act = tab[i * 4 + 3];
-    TORCH_CHECK(N >= 1 && K >= 1 && K == prev, "layer ", i, ": K=", K,
-                " does not chain from ", prev);
-    TORCH_CHECK(act >= FACT_NONE && act <= FACT_LEAKY, "layer ", i, ": bad act ", act);
-    const int npad = ceil_to(N, 16), kpad = ceil_to(K, 32);
-    const long wbytes = (long)npad * kpad * 2, bbytes = (long)npad * 4;
-    TORCH_CHECK(off == expect_off && off + wbytes + bbytes <= blob_bytes,
-                "layer ", i, ": offset ", off, " outside the packed blob");
-    t.l[i] = MlpLayer{off, (int)(off + wbytes), npad / 16, kpad / 32, act};
-    expect_off = off + wbytes + bbytes;
-    if (i > 0 && kpad > max_kpad) max_kpad = kpad;
-    prev = N;
-  }
-  TORCH_CHECK(expect_off == blob_bytes, "packed blob has trailing bytes");
-  TORCH_CHECK(prev == 1, "fused MLP needs a 1-unit head, got ", prev);
-  TORCH_CHECK(t.l[0].ks <= FMLP_MAX_KS0, "input width ", K0, " > ",
-              FMLP_MAX_KS0 * 32);
-  t.act_bytes = 32 * max_kpad;           // 16 rows x Kpad bf16
+  const MlpTable t = fmlp_parse_table(layer_table, K0, blob_bytes, FMLP_MAX_KS0);
   // eligibility is defined for the full 8-wave block
   const long lds_full = blob_bytes + 2L * FMLP_MAX_WAVES * t.act_bytes;
   TORCH_CHECK(lds_full <= FMLP_LDS_LIMIT, "fused MLP needs ", lds_full,

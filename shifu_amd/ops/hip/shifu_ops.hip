@@ -4155,6 +4155,14 @@ std::vector<at::Tensor> mlp_loss_grad_fused(
     at::Tensor x, at::Tensor target, at::Tensor weight,
     std::vector<at::Tensor> weights, std::vector<at::Tensor> biases,
     std::vector<int64_t> acts, int64_t kind, int64_t max_blocks);
+// device-side evaluation: loss + score histograms, AUC / KS — defined in eval_hist.hip
+void eval_hist_scores(at::Tensor logits, at::Tensor target, at::Tensor weight,
+                      at::Tensor state, int64_t n_bins, int64_t kind,
+                      int64_t replicas, int64_t max_blocks);
+void eval_hist_mlp(at::Tensor x, at::Tensor target, at::Tensor weight,
+                   at::Tensor packed, at::Tensor layer_table, at::Tensor state,
+                   int64_t n_bins, int64_t kind, int64_t max_blocks);
+void eval_hist_finish(at::Tensor state, int64_t n_bins);
 
 // ---------------------------------------------------------------------------
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -4208,4 +4216,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mlp_loss_grad_fused", &mlp_loss_grad_fused, py::arg("x"), py::arg("target"),
         py::arg("weight"), py::arg("weights"), py::arg("biases"), py::arg("acts"),
         py::arg("kind") = 0, py::arg("max_blocks") = 0);
+  m.def("eval_hist_scores", &eval_hist_scores, py::arg("logits"), py::arg("target"),
+        py::arg("weight"), py::arg("state"), py::arg("n_bins"), py::arg("kind") = 0,
+        py::arg("replicas") = 0, py::arg("max_blocks") = 0);
+  m.def("eval_hist_mlp", &eval_hist_mlp, py::arg("x"), py::arg("target"),
+        py::arg("weight"), py::arg("packed_weights"), py::arg("layer_table"),
+        py::arg("state"), py::arg("n_bins"), py::arg("kind") = 0,
+        py::arg("max_blocks") = 0);
+  m.def("eval_hist_finish", &eval_hist_finish, py::arg("state"), py::arg("n_bins"));
 }

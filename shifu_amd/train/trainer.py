@@ -296,6 +296,16 @@ class Trainer:
                 raise ValueError(f"fused_mlp_step is set but the model cannot "
                                  f"use the fused training step: {why}")
 
+        # loss + score histograms accumulated on the device (ops/eval_hist.py)
+        self._device_eval = bool(getattr(rc, "device_eval", False))
+        if self._device_eval:
+            from shifu_amd.ops.eval_hist import _check_bins
+            self._eval_bins = _check_bins(getattr(rc, "device_eval_bins", 1024))
+            if world_size != 1:
+                raise ValueError(
+                    f"device_eval is set but world size {world_size} != 1: the "
+                    f"per-rank evaluation states are not all-reduced yet")
+
     # ------------------------------------------------------------------ steps
     def train_step(self, batch: DeviceData, sync: bool = True) -> torch.Tensor:
         """One forward/backward/(all-reduce)/update step; returns the loss as
@@ -419,6 +429,8 @@ class Trainer:
         the SAME number of batches with the SAME batch size — ranks with
         fewer local rows pad with weight-0 repeats of row 0 (no-ops in the
         metrics)."""
+        if self._device_eval:
+            return self._evaluate_device(data, batch_size)
         self.model.eval()
         n = len(data)
         steps = (n + batch_size - 1) // batch_size
@@ -472,6 +484,33 @@ class Trainer:
         labels = data.target.cpu().numpy()[:len(scores)]
         return {"loss": total / max(wtot, 1e-12),
                 "auc": auc_score(scores, labels), "n": n}
+
+    @torch.no_grad()
+    def _evaluate_device(self, data: DeviceData, batch_size: int) -> dict:
+        """evaluate() with RunConfig.device_eval: the same batches, but loss and
+        score histograms accumulate on the device and the host reads one small
+        tensor at the end.  `auc` is the AUC of the bin-quantised scores; the
+        dict also carries ks, wauc, wks and the raw histograms."""
+        from shifu_amd.ops.eval_hist import EvalAccumulator, eval_eligible
+        from shifu_amd.ops.fused_mlp import pack_mlp
+        n = len(data)
+        acc = EvalAccumulator(self._eval_bins, self.device)
+        kind = 1 if self.loss_kind in ("sigmoid_ce", "ce", "bce") else 0
+        self.model.eval()
+        # an eligible MLP is packed once from the live parameters and runs
+        # forward + loss + histogram as one kernel per batch
+        packed = (pack_mlp(self.model)
+                  if eval_eligible(self.model, self._eval_bins)[0] else None)
+        idx_dev = ("cpu" if getattr(data, "index_device", "device") == "cpu"
+                   else self.device)
+        for s in range(0, n, batch_size):
+            b = data.slice(torch.arange(s, min(s + batch_size, n), device=idx_dev))
+            if packed is not None:
+                acc.add_mlp(packed, b.dense, b.target, b.weight, kind)
+            else:
+                acc.add_scores(self.model(b.dense, b.cats), b.target, b.weight, kind)
+        self.model.train()
+        return acc.result()
 
     # ------------------------------------------------------------------ epochs
     def run_epoch(self, epoch: int) -> TrainingIntermediateResult:
