@@ -21,6 +21,7 @@ setup(
             name="shifu_amd.ops._shifu_hip",
             sources=["shifu_amd/ops/hip/shifu_ops.hip",
                      "shifu_amd/ops/hip/fused_mlp.hip",
+                     "shifu_amd/ops/hip/fused_mlp_stream.hip",
                      "shifu_amd/ops/hip/fused_mlp_grad.hip",
                      "shifu_amd/ops/hip/eval_hist.hip"],
             extra_compile_args={

@@ -94,12 +94,23 @@ class PackedMLP:
     table: torch.Tensor       # CPU int32 [L, 4]: byte offset, N, K, act id
     lds_bytes: int
     num_features: int
+    kind: str = "resident"    # "resident": mlp_score_fused, weights in LDS;
+                              # "stream": mlp_score_stream, weights from L2
 
 
 def pack_mlp(model) -> PackedMLP:
     ok, why = fused_eligible(model)
     if not ok:
         raise ValueError(f"model is not eligible for fused scoring: {why}")
+    blob, table = _pack_layers(model)
+    return PackedMLP(blob=blob, table=table,
+                     lds_bytes=_lds_bytes([(r[1], r[2]) for r in table.tolist()]),
+                     num_features=_layers_of(model)[0].in_features)
+
+
+def _pack_layers(model):
+    """(blob on the model's device, CPU int32 [L, 4] table) in the per-layer
+    layout of the module docstring; no limit on the size of either."""
     layers = _layers_of(model)
     parts, rows, off = [], [], 0
     for l in layers:
@@ -114,11 +125,8 @@ def pack_mlp(model) -> PackedMLP:
         rows.append([off, n, k, l._act])
         off += npad * kpad * 2 + npad * 4
     blob = torch.cat(parts).contiguous()
-    device = layers[0].weight.device
-    return PackedMLP(blob=blob.to(device),
-                     table=torch.tensor(rows, dtype=torch.int32),
-                     lds_bytes=_lds_bytes([(r[1], r[2]) for r in rows]),
-                     num_features=layers[0].in_features)
+    return (blob.to(layers[0].weight.device),
+            torch.tensor(rows, dtype=torch.int32))
 
 
 def unpack_mlp(packed: PackedMLP, padded: bool = False):
@@ -166,11 +174,108 @@ def fused_predict(packed: PackedMLP, dense: torch.Tensor,
     return ext.mlp_score_fused(x, packed.blob, packed.table, max_blocks, waves)
 
 
+# ---------------------------------------------------------------------------
+# Nets that do not fit in LDS: `mlp_score_stream` (ops/hip/fused_mlp_stream.hip)
+# keeps only the activations of a BM-row block tile in LDS — two buffers, the
+# inputs of the even and of the odd layers — and streams the weights from
+# global memory (L2) into registers.  Same packed layout, same rounding
+# points, so `_emulate` serves both kernels.
+
+STREAM_LDS_LIMIT = 160 * 1024     # all of a gfx950 CU's LDS
+STREAM_MAX_WIDTH = 4096           # K0 and every layer width
+STREAM_ROW_TILES = (16, 32, 64)   # BM the kernel is built for
+
+
+def _stream_lds_bytes(shapes: List[Tuple[int, int]], row_tile: int) -> int:
+    """LDS of one block at a `row_tile`-row tile for layers [(N, K), ...]:
+    row_tile x the widest ceil32(K) among the even layers (buffer A) plus the
+    same among the odd layers (buffer B), in bf16 — the launcher re-derives it."""
+    a = max(_ceil_to(k, 32) for _, k in shapes[0::2])
+    b = max([0] + [_ceil_to(k, 32) for _, k in shapes[1::2]])
+    return row_tile * 2 * (a + b)
+
+
+def stream_eligible(model) -> Tuple[bool, str]:
+    """(True, "") when `model` can run through the streamed-weight kernel, else
+    (False, reason)."""
+    from shifu_amd.models.mlp import ShifuMLP
+    if not isinstance(model, ShifuMLP):
+        return False, (f"{type(model).__name__} is not a ShifuMLP (the streamed "
+                       f"scoring kernel covers dense MLP bundles only)")
+    layers = _layers_of(model)
+    if len(layers) > MAX_LAYERS:
+        return False, (f"{len(layers)} layers (head included) > {MAX_LAYERS}")
+    if layers[-1].out_features != 1:
+        return False, f"head width {layers[-1].out_features} != 1"
+    shapes = _shapes_of(model)
+    widest = max([shapes[0][1]] + [n for n, _ in shapes])
+    if widest > STREAM_MAX_WIDTH:
+        return False, f"width {widest} > {STREAM_MAX_WIDTH}"
+    lds = _stream_lds_bytes(shapes, STREAM_ROW_TILES[0])
+    if lds > STREAM_LDS_LIMIT:
+        return False, (f"activation buffers of a {STREAM_ROW_TILES[0]}-row tile "
+                       f"need {lds} B of LDS > {STREAM_LDS_LIMIT}")
+    return True, ""
+
+
+def pack_mlp_stream(model) -> PackedMLP:
+    """pack_mlp without the LDS and input-width limits; lds_bytes is the
+    block's LDS at the smallest row tile."""
+    ok, why = stream_eligible(model)
+    if not ok:
+        raise ValueError(f"model is not eligible for streamed scoring: {why}")
+    blob, table = _pack_layers(model)
+    return PackedMLP(blob=blob, table=table,
+                     lds_bytes=_stream_lds_bytes(_shapes_of(model),
+                                                 STREAM_ROW_TILES[0]),
+                     num_features=_layers_of(model)[0].in_features,
+                     kind="stream")
+
+
+@torch.no_grad()
+def stream_predict(packed: PackedMLP, dense: torch.Tensor, max_blocks: int = 0,
+                   row_tile: int = 0) -> torch.Tensor:
+    """Scores fp32 [B] for dense [B, num_features] (fp32 or bf16 rows) through
+    the streamed-weight kernel.  row_tile 0 lets the launcher choose the block
+    tile; 16, 32 or 64 forces it.  Scores do not depend on either argument."""
+    if dense.dim() != 2 or dense.shape[1] != packed.num_features:
+        raise ValueError(f"expected dense [B, {packed.num_features}], got "
+                         f"{tuple(dense.shape)}")
+    if row_tile not in (0,) + STREAM_ROW_TILES:
+        raise ValueError(f"row_tile must be 0 or one of {STREAM_ROW_TILES}, "
+                         f"got {row_tile}")
+    if not dense.is_cuda:
+        return _emulate(packed, dense)
+    ext = require_hip()
+    if ext is None:            # explicit eager A/B opt-in only (dispatch.py)
+        return _emulate(packed, dense)
+    if packed.blob.device != dense.device:
+        raise ValueError(f"packed weights are on {packed.blob.device} but the "
+                         f"rows are on {dense.device}")
+    x = dense.detach()
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        x = x.float()
+    return ext.mlp_score_stream(x.contiguous(), packed.blob, packed.table,
+                                max_blocks, row_tile)
+
+
 def attach_fused(model) -> PackedMLP:
-    """Pack `model` and route its predict() through the fused path."""
-    packed = pack_mlp(model)
+    """Pack `model` and route its predict() through a single-kernel path: the
+    LDS-resident kernel when `fused_eligible`, else the streamed-weight kernel
+    when `stream_eligible`; ValueError naming both reasons when neither."""
+    ok, why = fused_eligible(model)
+    if ok:
+        packed = pack_mlp(model)
+        model.predict = lambda dense, cats=None: fused_predict(packed, dense)
+    else:
+        ok, why_stream = stream_eligible(model)
+        if not ok:
+            raise ValueError(f"model is not eligible for fused scoring: "
+                             f"resident kernel: {why}; streamed kernel: "
+                             f"{why_stream}")
+        packed = pack_mlp_stream(model)
+        model.predict = lambda dense, cats=None: stream_predict(packed, dense)
     model._fused_packed = packed
-    model.predict = lambda dense, cats=None: fused_predict(packed, dense)
     return packed
 
 

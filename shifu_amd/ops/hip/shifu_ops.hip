@@ -4150,6 +4150,10 @@ at::Tensor mlp_score_fused(at::Tensor x, at::Tensor packed,
 std::vector<at::Tensor> mlp_score_fused_ensemble(
     at::Tensor x, std::vector<at::Tensor> blobs, std::vector<at::Tensor> tables,
     bool return_members, int64_t max_blocks, int64_t waves);
+// streamed-weight scoring for nets that do not fit in LDS — defined in fused_mlp_stream.hip
+at::Tensor mlp_score_stream(at::Tensor x, at::Tensor packed,
+                            at::Tensor layer_table, int64_t max_blocks,
+                            int64_t row_tile);
 // fused forward+loss+backward of an LDS-resident MLP — defined in fused_mlp_grad.hip
 std::vector<at::Tensor> mlp_loss_grad_fused(
     at::Tensor x, at::Tensor target, at::Tensor weight,
@@ -4213,6 +4217,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mlp_score_fused_ensemble", &mlp_score_fused_ensemble, py::arg("x"),
         py::arg("blobs"), py::arg("tables"), py::arg("return_members") = false,
         py::arg("max_blocks") = 0, py::arg("waves") = 8);
+  m.def("mlp_score_stream", &mlp_score_stream, py::arg("x"), py::arg("packed_weights"),
+        py::arg("layer_table"), py::arg("max_blocks") = 0, py::arg("row_tile") = 0);
   m.def("mlp_loss_grad_fused", &mlp_loss_grad_fused, py::arg("x"), py::arg("target"),
         py::arg("weight"), py::arg("weights"), py::arg("biases"), py::arg("acts"),
         py::arg("kind") = 0, py::arg("max_blocks") = 0);

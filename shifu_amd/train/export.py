@@ -197,10 +197,14 @@ def load_exported(final_model_path: str, device: str = "cpu",
                   fused=False) -> torch.nn.Module:
     """Reconstruct an exported model from graph.json + weights (the scorer path).
 
-    fused=True routes predict() of an eligible `mlp` bundle through the
-    single-kernel scoring path (ops/fused_mlp.py) and raises ValueError with
-    the reason on an ineligible one; fused="auto" quietly keeps the layer
-    path there; fused=False (default) never touches the fused path."""
+    fused=True routes predict() of an `mlp` bundle through a single-kernel
+    scoring path (ops/fused_mlp.py): the LDS-resident kernel when the net fits
+    it, else the streamed-weight kernel; it raises ValueError naming both
+    kernels' reasons when neither applies.  fused="auto" takes the resident
+    kernel or quietly keeps the layer path; it never picks the streamed
+    kernel, because whether that beats the tiled GEMMs at large batches is a
+    measurement "auto" does not have yet (profiles/streamed_mlp_scoring.md).
+    fused=False (default) never touches the fused path."""
     if fused not in (False, True, "auto"):
         raise ValueError(f"fused must be False, True or 'auto', got {fused!r}")
     if os.path.exists(os.path.join(final_model_path, ENSEMBLE_FILE)):
@@ -232,11 +236,15 @@ def load_exported(final_model_path: str, device: str = "cpu",
     model.load_state_dict(state)
     model = model.to(device).eval()
     if fused:
-        from shifu_amd.ops.fused_mlp import attach_fused, fused_eligible
+        from shifu_amd.ops.fused_mlp import (attach_fused, fused_eligible,
+                                             stream_eligible)
         ok, why = fused_eligible(model)
+        if not ok and fused is True:
+            ok, why_stream = stream_eligible(model)
+            if not ok:
+                raise ValueError(f"{final_model_path}: fused scoring unavailable "
+                                 f"for this {fam} bundle: resident kernel: {why}; "
+                                 f"streamed kernel: {why_stream}")
         if ok:
             attach_fused(model)
-        elif fused is True:
-            raise ValueError(f"{final_model_path}: fused scoring unavailable "
-                             f"for this {fam} bundle: {why}")
     return model
