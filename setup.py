@@ -22,6 +22,7 @@ setup(
             sources=["shifu_amd/ops/hip/shifu_ops.hip",
                      "shifu_amd/ops/hip/fused_mlp.hip",
                      "shifu_amd/ops/hip/fused_mlp_stream.hip",
+                     "shifu_amd/ops/hip/fused_wide_deep.hip",
                      "shifu_amd/ops/hip/fused_mlp_grad.hip",
                      "shifu_amd/ops/hip/eval_hist.hip"],
             extra_compile_args={

@@ -143,16 +143,22 @@ def unpack_mlp(packed: PackedMLP, padded: bool = False):
     return out
 
 
-def _emulate(packed: PackedMLP, dense: torch.Tensor) -> torch.Tensor:
-    """Pure-torch forward pass with exactly the kernel's rounding points."""
+def _emulate_logit(packed, dense: torch.Tensor) -> torch.Tensor:
+    """The fp32 head logit [B] (CPU) of a pure-torch forward pass with exactly
+    the kernel's rounding points; `packed` needs only .blob and .table."""
     layers = unpack_mlp(packed)
     x = dense.detach().float().cpu().to(torch.bfloat16).float()
     for i, (w, b, act) in enumerate(layers):
         z = x @ w.float().t() + b
         if i == len(layers) - 1:
-            return torch.sigmoid(z.reshape(-1)).to(dense.device)
+            return z.reshape(-1)
         x = _act_fwd_ref(z, act).to(torch.bfloat16).float()
     raise AssertionError("unreachable")
+
+
+def _emulate(packed: PackedMLP, dense: torch.Tensor) -> torch.Tensor:
+    """Pure-torch forward pass with exactly the kernel's rounding points."""
+    return torch.sigmoid(_emulate_logit(packed, dense)).to(dense.device)
 
 
 @torch.no_grad()

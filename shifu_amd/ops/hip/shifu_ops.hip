@@ -4154,6 +4154,12 @@ std::vector<at::Tensor> mlp_score_fused_ensemble(
 at::Tensor mlp_score_stream(at::Tensor x, at::Tensor packed,
                             at::Tensor layer_table, int64_t max_blocks,
                             int64_t row_tile);
+// Wide&Deep scoring (fold, gather, wide term, tower, head) — defined in fused_wide_deep.hip
+at::Tensor wd_score_stream(at::Tensor dense, at::Tensor ids, at::Tensor arena,
+                           at::Tensor wide_vec, at::Tensor wd_w, double wide_bias,
+                           at::Tensor feat_table, at::Tensor feat_table_dev,
+                           at::Tensor packed, at::Tensor layer_table,
+                           int64_t max_blocks, int64_t row_tile);
 // fused forward+loss+backward of an LDS-resident MLP — defined in fused_mlp_grad.hip
 std::vector<at::Tensor> mlp_loss_grad_fused(
     at::Tensor x, at::Tensor target, at::Tensor weight,
@@ -4218,6 +4224,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("blobs"), py::arg("tables"), py::arg("return_members") = false,
         py::arg("max_blocks") = 0, py::arg("waves") = 8);
   m.def("mlp_score_stream", &mlp_score_stream, py::arg("x"), py::arg("packed_weights"),
+        py::arg("layer_table"), py::arg("max_blocks") = 0, py::arg("row_tile") = 0);
+  m.def("wd_score_stream", &wd_score_stream, py::arg("dense"), py::arg("ids"),
+        py::arg("arena"), py::arg("wide_vec"), py::arg("wd_w"), py::arg("wide_bias"),
+        py::arg("feat_table"), py::arg("feat_table_dev"), py::arg("packed_weights"),
         py::arg("layer_table"), py::arg("max_blocks") = 0, py::arg("row_tile") = 0);
   m.def("mlp_loss_grad_fused", &mlp_loss_grad_fused, py::arg("x"), py::arg("target"),
         py::arg("weight"), py::arg("weights"), py::arg("biases"), py::arg("acts"),

@@ -8,7 +8,7 @@ score per row, and optionally report AUC against the target column.
     python -m shifu_amd.score --model final_model/ \
         --data part-*.csv.gz --column-config ColumnConfig.json \
         --output scores.csv [--auc] [--batch 65536] [--device cpu|cuda]
-        [--fused off|on|auto] [--member-scores]
+        [--fused off|on|auto] [--fused-wd off|on] [--member-scores]
 
 --model also accepts a bagged model set (a directory with ensemble.json and
 model0/ .. modelN-1/, written by export_ensemble): the score is the members'
@@ -40,17 +40,19 @@ import numpy as np
 def score_files(model_dir: str, data_paths: List[str],
                 column_config: Optional[str] = None, batch: int = 65536,
                 device: str = "cpu", delimiter: str = "|", fused=False,
-                member_scores: bool = False):
+                member_scores: bool = False, fused_wd: bool = False):
     """Returns (scores np[N], targets np[N] or None), and with
     member_scores=True a third item, the per-member scores np[N, M] (M = 1
     for a single bundle).  fused: False | True | "auto" — the single-kernel
-    MLP scoring path (see load_exported)."""
+    MLP scoring path; fused_wd: False | True — the single-kernel Wide&Deep
+    scoring path (see load_exported for both)."""
     import torch
     from shifu_amd.train.export import (ENSEMBLE_FILE, ensemble_member_dirs,
                                         load_exported)
     from shifu_amd.io import load_csv_native
 
-    model = load_exported(model_dir, device=device, fused=fused)
+    model = load_exported(model_dir, device=device, fused=fused,
+                          fused_wd=fused_wd)
     spec_dir = model_dir
     if os.path.exists(os.path.join(model_dir, ENSEMBLE_FILE)):
         spec_dir = ensemble_member_dirs(model_dir)[0]
@@ -124,6 +126,9 @@ def main(argv=None) -> int:
     ap.add_argument("--fused", choices=["off", "on", "auto"], default="off",
                     help="single-kernel scoring for MLP bundles: 'on' errors "
                          "on an ineligible bundle, 'auto' keeps the layer path")
+    ap.add_argument("--fused-wd", choices=["off", "on"], default="off",
+                    help="single-kernel scoring for Wide&Deep bundles: 'on' "
+                         "errors on any other bundle")
     ap.add_argument("--member-scores", action="store_true",
                     help="append the per-member scores of an ensemble to each "
                          "output line (delimiter-separated, member order)")
@@ -156,7 +161,8 @@ def main(argv=None) -> int:
                           args.batch, args.device, args.delimiter,
                           fused={"off": False, "on": True,
                                  "auto": "auto"}[args.fused],
-                          member_scores=args.member_scores)
+                          member_scores=args.member_scores,
+                          fused_wd=args.fused_wd == "on")
         scores, targets = res[0], res[1]
         if args.member_scores:
             members = res[2]

@@ -39,9 +39,11 @@ class ShifuScorer:
         self.device = "cpu"
 
     def init(self, generic_model_config_path: str, device: str = "cpu",
-             fused=False) -> None:
+             fused=False, fused_wd=False) -> None:
         """fused (False | True | "auto") is forwarded to load_exported: the
-        single-kernel MLP scoring path (ops/fused_mlp.py)."""
+        single-kernel MLP scoring path (ops/fused_mlp.py).  fused_wd (False |
+        True) likewise: the single-kernel Wide&Deep scoring path
+        (ops/fused_wide_deep.py)."""
         with open(generic_model_config_path) as f:
             gmc = json.load(f)
         if gmc.get("outputnames", ["shifu_output_0"])[0] != "shifu_output_0":
@@ -57,6 +59,9 @@ class ShifuScorer:
             if os.path.exists(os.path.join(d, ENSEMBLE_FILE)):
                 from shifu_amd.train.export import load_exported_ensemble
                 self.model = load_exported_ensemble(d, device=device, fused=fused)
+                if fused_wd:
+                    from shifu_amd.train.export import attach_fused_wd_or_raise
+                    attach_fused_wd_or_raise(self.model, d)
                 self.device = device
                 with open(os.path.join(ensemble_member_dirs(d)[0],
                                        "graph.json")) as f:
@@ -68,7 +73,8 @@ class ShifuScorer:
         gj = os.path.join(model_path, "graph.json")
         if os.path.exists(gj):
             from shifu_amd.train.export import load_exported
-            self.model = load_exported(model_path, device=device, fused=fused)
+            self.model = load_exported(model_path, device=device, fused=fused,
+                                       fused_wd=fused_wd)
             self.device = device
             with open(gj) as f:
                 spec = json.load(f)
@@ -78,7 +84,7 @@ class ShifuScorer:
         # no portable layout: score straight from the TF SavedModel artifact
         # (the same file the Java SavedModelBundle path loads)
         pb = os.path.join(model_path, "saved_model.pb")
-        if fused is True:
+        if fused is True or fused_wd:
             raise ValueError(f"{model_path}: fused scoring needs the portable "
                              f"graph.json bundle")
         if not os.path.exists(pb):

@@ -193,8 +193,19 @@ def load_exported_ensemble(final_model_path: str, device: str = "cpu",
     return model
 
 
+def attach_fused_wd_or_raise(model: torch.nn.Module, final_model_path: str):
+    """The fused_wd=True step of load_exported: route predict() through the
+    fused Wide&Deep kernel, or ValueError with wd_eligible's reason."""
+    from shifu_amd.ops.fused_wide_deep import attach_fused_wd, wd_eligible
+    ok, why = wd_eligible(model)
+    if not ok:
+        raise ValueError(f"{final_model_path}: fused Wide&Deep scoring "
+                         f"unavailable for this bundle: {why}")
+    attach_fused_wd(model)
+
+
 def load_exported(final_model_path: str, device: str = "cpu",
-                  fused=False) -> torch.nn.Module:
+                  fused=False, fused_wd=False) -> torch.nn.Module:
     """Reconstruct an exported model from graph.json + weights (the scorer path).
 
     fused=True routes predict() of an `mlp` bundle through a single-kernel
@@ -204,11 +215,22 @@ def load_exported(final_model_path: str, device: str = "cpu",
     kernel or quietly keeps the layer path; it never picks the streamed
     kernel, because whether that beats the tiled GEMMs at large batches is a
     measurement "auto" does not have yet (profiles/streamed_mlp_scoring.md).
-    fused=False (default) never touches the fused path."""
+    fused=False (default) never touches the fused path.
+
+    fused_wd=True is the separate switch of the fused Wide&Deep kernel
+    (ops/fused_wide_deep.py): it routes predict() of a `wide_deep` bundle
+    through one launch per batch and raises ValueError with wd_eligible's
+    reason for anything else (mlp and deepfm bundles, ensembles).  It does not
+    change what `fused` does, which keeps refusing Wide&Deep."""
     if fused not in (False, True, "auto"):
         raise ValueError(f"fused must be False, True or 'auto', got {fused!r}")
+    if fused_wd not in (False, True):
+        raise ValueError(f"fused_wd must be False or True, got {fused_wd!r}")
     if os.path.exists(os.path.join(final_model_path, ENSEMBLE_FILE)):
-        return load_exported_ensemble(final_model_path, device=device, fused=fused)
+        model = load_exported_ensemble(final_model_path, device=device, fused=fused)
+        if fused_wd:
+            attach_fused_wd_or_raise(model, final_model_path)
+        return model
     from shifu_amd.models.mlp import ShifuMLP
     from shifu_amd.models.wide_deep import WideDeep
     from shifu_amd.models.deepfm import DeepFM
@@ -247,4 +269,6 @@ def load_exported(final_model_path: str, device: str = "cpu",
                                  f"streamed kernel: {why_stream}")
         if ok:
             attach_fused(model)
+    if fused_wd:
+        attach_fused_wd_or_raise(model, final_model_path)
     return model
